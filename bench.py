@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: Mrays/s + ms/frame of the trace path on BASELINE.json config C2.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed steps, the result line
+(value, ms_per_step, the configuration, the host-side medians of the timed calls).  --full adds everything that
+takes runs of its own after the timed region: the serialised launches and work-counting passes of the roofline
+block, the synchronous latency frames, the per-frame rebuild's stage roofline and the CPU baseline.
+--dump-outputs DIR writes the frame the last timed step rendered (what the caller's RGBA8 buffer holds) to
+DIR/frame_rgba8.npy; the scene, the camera and the frame seeds are fixed, so two builds can be compared pixel for pixel.
 
 A step is one frame of the reference's render loop (src/Global/Renderer.cu:264-317): the
 instance update callback (Main.cu updateInstance, native), the host TLAS rebuild + upload,
@@ -39,6 +46,11 @@ B_PAIR, B_TRI, B_SPH, B_QUAD, B_INST, B_HIT, B_PIXEL = 64, 48, 16, 80, 80, 208, 
 # measured HBM fraction below which the kernel is reported latency-bound
 LATENCY_BOUND_FRAC = 0.25
 PMC_DIR = os.path.join(REPO, "profiles", "pmc")
+RING = 256                     # rt_api.cpp: the library's per-frame kernel-time ring keeps the last 256 launches
+# --dump-outputs: a frame of more pixels is written as a seeded sample of this many (16 B of float32 RGBA + 8 B of
+# float64 index per pixel: 48 MB; a whole 2 Mi-pixel frame is 32 MB)
+DUMP_MAX_PIXELS = 2 << 20
+DUMP_SEED = 0
 
 
 # width, height, requested spp per config (read before HIP starts; checked against rtamd.scenes.CONFIGS in main)
@@ -52,7 +64,14 @@ def parse():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--config", default="C2")
-    p.add_argument("--exact", action="store_true", help="time the EXACT (parity) kernel instead of FAST")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the roofline's serialised launches and work-counting passes, the "
+                        "latency frames, the rebuild's stage roofline (--rebuild) and the CPU baseline (--steps above 256: the "
+                        "roofline covers the last 256 timed frames, the library's per-frame kernel-time ring)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write the frame of the last timed step to DIR/frame_rgba8.npy (float32; frames above "
+                        f"{DUMP_MAX_PIXELS} pixels: a fixed seeded pixel sample, its indices in frame_pixel_index.npy)")
+    p.add_argument("--exact",action="store_true", help="time the EXACT (parity) kernel instead of FAST")
     p.add_argument("--build", default="sah", choices=("sah", "compat", "lbvh"),
                    help="BVH builder: SAH (default), the reference's random-axis median split, or the GPU LBVH builder")
     p.add_argument("--rebuild", action="store_true", help="--build lbvh: rebuild every BLAS on the GPU each frame (C5)")
@@ -77,8 +96,8 @@ def parse():
     p.add_argument("--tile", type=int, default=32, help="N > 1 screen-tile edge in pixels (multiple of 8)")
     p.add_argument("--attach-comm", action="store_true",
                    help="N = 1: run the multi-GPU frame path anyway (a world-1 RCCL communicator: tiles + assemble)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--cpu-seconds", type=float, default=12.0)
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: the CPU baseline's time budget")
     p.add_argument("--clock-warmup", type=float, default=0.5,
                    help="seconds of untimed frames before the W warm-up steps (the GPU's clocks ramp up under load)")
     p.add_argument("--print-pmc-tag", action="store_true", help="print this run's PMC tag as JSON and exit (no GPU)")
@@ -101,6 +120,20 @@ def layout_bytes(st):
     return (B_PAIR * st["aabb_tests"] / 2 + B_TRI * st["triangle_tests"] + B_SPH * spheres +
             B_QUAD * st["quad_tests"] + B_INST * st["instance_visits"] + B_HIT * st["hits"] +
             B_PIXEL * st["pixels"])
+
+
+def dump_outputs(out_dir, frame_rgba8, width, height):
+    """--dump-outputs: the RGBA8 frame the last timed step left in the caller's buffer (a uint8 tensor of
+    width * height * 4), as float32 [pixels, 4] (row-major pixels, values 0..255).  A frame above DUMP_MAX_PIXELS is
+    sampled: DUMP_MAX_PIXELS pixel indices drawn once from numpy's default_rng(DUMP_SEED), sorted, the same every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    px = frame_rgba8.cpu().numpy().reshape(height * width, 4)
+    if height * width > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(height * width, DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+        px = px[idx]
+    np.save(os.path.join(out_dir, "frame_rgba8.npy"), px.astype(np.float32))
 
 
 def host_cores():
@@ -274,8 +307,8 @@ def main():
     if args.print_pmc_tag:
         print(json.dumps(pmc_tag(args)))
         return
-    if not 1 <= args.steps <= 256:
-        raise SystemExit("--steps must be in 1..256 (the library's per-frame kernel-time ring)")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     global TILE
     TILE = args.tile
     if TILE % 8 or TILE <= 0:
@@ -428,7 +461,8 @@ def main():
             break
     for f in range(args.warmup):                           # pipelined like the timed steps (and in the timing ring)
         step(f, sync=False)
-        pre_frames.append(f)
+        if f >= args.warmup - RING:                        # (the ring keeps the last RING launches)
+            pre_frames.append(f)
     torch.cuda.synchronize()
     if n > 1:
         dist.barrier()
@@ -451,7 +485,10 @@ def main():
     if lib_lanes and args.overlap is None:
         L = int(r.info()["overlap_lanes"])                 # the library's pick for this frame kind
     rays = int(acc["rays"])
-    assert len(kernel_ms) == args.steps, (len(kernel_ms), args.steps)
+    assert len(kernel_ms) == min(args.steps, RING), (len(kernel_ms), args.steps)
+    if args.dump_outputs and rank == 0:                    # the last timed frame, before anything renders again
+        last = args.warmup + args.steps - 1
+        dump_outputs(args.dump_outputs, frame_bufs[last % nbuf if overlap else 0], cfg.width, cfg.height)
 
     # max over ranks of the elapsed time; total rays over ranks
     if n > 1:
@@ -460,81 +497,11 @@ def main():
         dist.all_reduce(tmax[:1], op=dist.ReduceOp.MAX)
         dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         elapsed, rays = float(tmax[0]), int(t[1])
+    value = rays / elapsed / 1e6
 
-    # the roofline's serialised launches: the timed frames again, back to back on one stream (no overlap partner,
-    # so each launch has the whole GPU: "grid_pct" 100), the GPU kept busy so its clocks stay where the timed
-    # region ran them; the HIP-event duration of each launch is the kernel's own
-    if overlap:
-        r.set_option("grid_pct", 100)
-    for k in range(args.steps):
-        step(args.warmup + k, sync=False, one_stream=True)
-    torch.cuda.synchronize()
-    _, serial_ms = r.collect()
-    if overlap:
-        r.set_option("grid_pct", 0)
-    if n > 1:
-        dist.barrier()
-    # SURVEY 8d latency definition: wall time from the call to the framebuffer being ready (rank 0: the
-    # assembled frame), synchronous frames, median of 20 after the timed region (untimed for `value`)
-    lat = []
-    n_lat = min(20, args.steps)
-    for k in range(n_lat):                                 # the first timed frames, one at a time
-        t1 = time.perf_counter()
-        step(args.warmup + k, sync=False)                  # enqueue, then wait for the whole device
-        torch.cuda.synchronize()
-        lat.append((time.perf_counter() - t1) * 1e3)
-    _, sync_ms = r.collect()
-    if n > 1:
-        dist.barrier()
-
-    # untimed work-counting passes for the roofline: the animation changes a frame's work (C3's launches vary
-    # 1.3-2.6 ms over the frames of one run), so every priced launch is priced with the work of the frame it
-    # rendered — one counting pass per distinct frame (all ranks run the same passes: a pass gathers too)
-    timed_frames = [args.warmup + k for k in range(args.steps)]
-    serial_frames = list(timed_frames)                       # the serialised launches re-render the timed frames
-    lat_frames = timed_frames[:n_lat]
-    all_serial = not overlap                                 # every launch of the run was serialised
-    priced_frames = (pre_frames + timed_frames + serial_frames + lat_frames) if all_serial else serial_frames
-    assert not all_serial or len(priced_frames) == len(pre_ms) + len(kernel_ms) + len(serial_ms) + len(sync_ms), \
-        (len(pre_frames), len(pre_ms), len(kernel_ms), len(serial_ms), len(sync_ms))
-    work = {}
-    torch.cuda.synchronize()
-    for f in sorted(set(priced_frames + timed_frames)):
-        _, _, work[f] = r.render(f, exact=args.exact, want_rgba=False, count_work=True,
-                                 rgba8_device=frame_buf.data_ptr() if frame_buf is not None else None, tiles=tiles,
-                                 stream=stream)
-    if n > 1:
-        dist.barrier()
-    # the per-frame BLAS rebuild's own roofline (untimed; every rank rebuilds its replica, so rank 0's is the figure)
-    rebuild_block = None
-    if args.rebuild and not args.no_rebuild_roofline:
-        torch.cuda.synchronize()
-        r.synchronize()
-        rebuild_block = rebuild_roofline(r, [args.warmup + args.steps + k for k in range(6)])
-    if n > 1:
-        dist.barrier()
-
-    if rank == 0:
-        avg_kernel_ms = float(np.mean(kernel_ms))            # timed region: launches overlap (L lanes)
-        serial_kernel_ms = float(np.mean(serial_ms))         # the same kernel with no overlap partner, back to back
-        sync_kernel_ms = float(np.mean(sync_ms))             # ... and after a host synchronisation each (latency frames)
-        if all_serial:
-            every = list(pre_ms) + list(kernel_ms) + list(serial_ms) + list(sync_ms)
-            serial_kernel_ms = float(np.mean(every))
-        # mean over the priced launches of their frames' counted work
-        keys = ("rays", "pixels", "aabb_tests", "triangle_tests", "sphere_quad_tests", "quad_tests", "instance_visits", "hits")
-        cst = {k: float(np.mean([work[f][k] for f in priced_frames])) for k in keys}
-        bytes_launch = float(np.mean([algorithmic_bytes(work[f]) for f in priced_frames]))
-        bytes_timed = float(np.mean([algorithmic_bytes(work[f]) for f in timed_frames]))
-        achieved = bytes_launch / (serial_kernel_ms * 1e-3) / 1e9
-        kname = ("render_persistent_kernel" if args.kernel else "render_kernel") + ("<exact>" if args.exact else "<fast>")
-        tag = pmc_tag(args)
-        traffic, traffic_src, traffic_why = load_traffic(tag)
-        hbm_frac = traffic / (serial_kernel_ms * 1e-3) / (HBM_PEAK_GBS * 1e9) if traffic else None
-        # what the counters say limits the kernel (null without a PMC summary of this exact workload)
-        limiter = ("latency" if hbm_frac < LATENCY_BOUND_FRAC else "hbm") if hbm_frac is not None else None
-        value = rays / elapsed / 1e6
-        out = {
+    def headline():
+        """The result line of a plain run: the timed region's figures and the configuration (--full adds its blocks)."""
+        return {
             "metric": METRIC,
             "value": round(value, 2),
             "unit": "Mrays/s",
@@ -547,6 +514,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": bool(args.full),
             "config": {
                 "workload": f"{cfg.name}: {cfg.description}",
                 "width": cfg.width, "height": cfg.height, "spp": cfg.spp, "depth": cfg.depth,
@@ -574,16 +542,9 @@ def main():
                           (", per-frame GPU BLAS rebuild" if args.rebuild else "") + ", pipelined",
             },
             "value_kind": (f"whole-frame throughput with {L} overlapped lanes (frame k+1's launch fills frame k's "
-                           "tail); frame_latency_ms_median is the synchronous call-to-framebuffer time") if overlap
+                           "tail); frame_latency_ms_median (--full) is the synchronous call-to-framebuffer time") if overlap
                           else "whole-frame throughput, serialised frames",
             "rays_per_frame": round(rays / args.steps, 1),
-            "frame_latency_ms_median": round(float(np.median(lat)), 4),
-            # SURVEY 8(d) as a rate: the latency frames' rays (counted) over the median synchronous call-to-framebuffer
-            # time (one frame in flight, as the reference's loop keeps on its render stream, Renderer.cu:308-317)
-            # (N > 1: rank 0 counted only its own tiles, so the timed frames' mean over all ranks is used)
-            "value_latency": round((float(np.mean([work[f]["rays"] for f in lat_frames])) if n == 1 else rays / args.steps)
-                                   / (float(np.median(lat)) * 1e-3) / 1e6, 2),
-            "value_latency_unit": "Mrays/s",
             # host side of a timed rt_render call (update callback, instance records, TLAS build, staging)
             # and the part of it spent blocked on the GPU (a staging buffer still in use)
             "host_update_ms_median": round(float(np.median(timed_update[:, 0])), 4),
@@ -594,10 +555,106 @@ def main():
             "host_busy_ms_median": round(float(np.median(timed_update[:, 2] - timed_update[:, 1])), 4),
             "host_call_ms_mean": round(float(np.mean(timed_update[:, 2])), 4),
             "host_update_wait_ms_mean": round(float(np.mean(timed_update[:, 1])), 4),
-            "kernel_ms": round(serial_kernel_ms, 4),
-            "kernel_ms_overlapped": round(avg_kernel_ms, 4),
-            "kernel_ms_sync": round(sync_kernel_ms, 4),
+            # the timed region's launches (they overlap on the L lanes), the last RING of them
+            "kernel_ms_overlapped": round(float(np.mean(kernel_ms)), 4),
             "clock_warmup_s": args.clock_warmup,
+        }
+
+    def finish():
+        if n > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        r.cleanup()
+
+    if not args.full:                                      # a plain run ends here
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        finish()
+        return
+
+    # the roofline's serialised launches: the timed frames again, back to back on one stream (no overlap partner,
+    # so each launch has the whole GPU: "grid_pct" 100), the GPU kept busy so its clocks stay where the timed
+    # region ran them; the HIP-event duration of each launch is the kernel's own
+    # (--steps above the library's timing ring: the last RING timed frames, whose launch times the ring still holds)
+    timed_frames = [args.warmup + k for k in range(args.steps)][-RING:]
+    if overlap:
+        r.set_option("grid_pct", 100)
+    for f in timed_frames:
+        step(f, sync=False, one_stream=True)
+    torch.cuda.synchronize()
+    _, serial_ms = r.collect()
+    if overlap:
+        r.set_option("grid_pct", 0)
+    if n > 1:
+        dist.barrier()
+    # SURVEY 8d latency definition: wall time from the call to the framebuffer being ready (rank 0: the
+    # assembled frame), synchronous frames, median of 20 after the timed region (untimed for `value`)
+    lat = []
+    n_lat = min(20, args.steps)
+    for k in range(n_lat):                                 # the first timed frames, one at a time
+        t1 = time.perf_counter()
+        step(args.warmup + k, sync=False)                  # enqueue, then wait for the whole device
+        torch.cuda.synchronize()
+        lat.append((time.perf_counter() - t1) * 1e3)
+    _, sync_ms = r.collect()
+    if n > 1:
+        dist.barrier()
+
+    # untimed work-counting passes for the roofline: the animation changes a frame's work (C3's launches vary
+    # 1.3-2.6 ms over the frames of one run), so every priced launch is priced with the work of the frame it
+    # rendered — one counting pass per distinct frame (all ranks run the same passes: a pass gathers too)
+    serial_frames = list(timed_frames)                       # the serialised launches re-render the timed frames
+    lat_frames = [args.warmup + k for k in range(n_lat)]
+    all_serial = not overlap                                 # every launch of the run was serialised
+    priced_frames = (pre_frames + timed_frames + serial_frames + lat_frames) if all_serial else serial_frames
+    assert not all_serial or len(priced_frames) == len(pre_ms) + len(kernel_ms) + len(serial_ms) + len(sync_ms), \
+        (len(pre_frames), len(pre_ms), len(kernel_ms), len(serial_ms), len(sync_ms))
+    work = {}
+    torch.cuda.synchronize()
+    for f in sorted(set(priced_frames + timed_frames + lat_frames)):
+        _, _, work[f] = r.render(f, exact=args.exact, want_rgba=False, count_work=True,
+                                 rgba8_device=frame_buf.data_ptr() if frame_buf is not None else None, tiles=tiles,
+                                 stream=stream)
+    if n > 1:
+        dist.barrier()
+    # the per-frame BLAS rebuild's own roofline (untimed; every rank rebuilds its replica, so rank 0's is the figure)
+    rebuild_block = None
+    if args.rebuild and not args.no_rebuild_roofline:
+        torch.cuda.synchronize()
+        r.synchronize()
+        rebuild_block = rebuild_roofline(r, [args.warmup + args.steps + k for k in range(6)])
+    if n > 1:
+        dist.barrier()
+
+    if rank == 0:
+        serial_kernel_ms = float(np.mean(serial_ms))         # the same kernel with no overlap partner, back to back
+        sync_kernel_ms = float(np.mean(sync_ms))             # ... and after a host synchronisation each (latency frames)
+        if all_serial:
+            every = list(pre_ms) + list(kernel_ms) + list(serial_ms) + list(sync_ms)
+            serial_kernel_ms = float(np.mean(every))
+        # mean over the priced launches of their frames' counted work
+        keys = ("rays", "pixels", "aabb_tests", "triangle_tests", "sphere_quad_tests", "quad_tests", "instance_visits", "hits")
+        cst = {k: float(np.mean([work[f][k] for f in priced_frames])) for k in keys}
+        bytes_launch = float(np.mean([algorithmic_bytes(work[f]) for f in priced_frames]))
+        bytes_timed = float(np.mean([algorithmic_bytes(work[f]) for f in timed_frames]))
+        achieved = bytes_launch / (serial_kernel_ms * 1e-3) / 1e9
+        kname = ("render_persistent_kernel" if args.kernel else "render_kernel") + ("<exact>" if args.exact else "<fast>")
+        tag = pmc_tag(args)
+        traffic, traffic_src, traffic_why = load_traffic(tag)
+        hbm_frac = traffic / (serial_kernel_ms * 1e-3) / (HBM_PEAK_GBS * 1e9) if traffic else None
+        # what the counters say limits the kernel (null without a PMC summary of this exact workload)
+        limiter = ("latency" if hbm_frac < LATENCY_BOUND_FRAC else "hbm") if hbm_frac is not None else None
+        out = headline()
+        out.update({
+            "frame_latency_ms_median": round(float(np.median(lat)), 4),
+            # SURVEY 8(d) as a rate: the latency frames' rays (counted) over the median synchronous call-to-framebuffer
+            # time (one frame in flight, as the reference's loop keeps on its render stream, Renderer.cu:308-317)
+            # (N > 1: rank 0 counted only its own tiles, so the timed frames' mean over all ranks is used)
+            "value_latency": round((float(np.mean([work[f]["rays"] for f in lat_frames])) if n == 1 else rays / args.steps)
+                                   / (float(np.median(lat)) * 1e-3) / 1e6, 2),
+            "value_latency_unit": "Mrays/s",
+            "kernel_ms": round(serial_kernel_ms, 4),
+            "kernel_ms_sync": round(sync_kernel_ms, 4),
             "roofline": {
                 "bound": "hbm",                                   # the roof `achieved` is priced against
                 "limiter": limiter,
@@ -628,16 +685,13 @@ def main():
                                 f"distinct frames, mean over the {len(priced_frames)} priced launches)"),
             },
             "cpu_baseline": None,
-        }
+        })
         if rebuild_block is not None:
             out["rebuild"] = rebuild_block
         if n == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, cfg, args.cpu_seconds)
         print(json.dumps(out), flush=True)
-    if n > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    r.cleanup()
+    finish()
 
 
 if __name__ == "__main__":

@@ -22,12 +22,12 @@ for rep in $(seq 1 $REPS); do
     for v in ${VALS:-0 1}; do
       if [ "$OPT" = lib ]; then
         if [ "$v" = default ]; then lib=""; else lib=$PWD/real-time-gpu-ray-tracer_amd/lib/librtamd_$v.so; fi
-        RTAMD_LIB=$lib timeout -k 10 300 python3 bench.py $args --no-cpu-baseline > $OUT/${name}_${v}_$rep.log 2>&1
+        RTAMD_LIB=$lib timeout -k 10 300 python3 bench.py $args --full --no-cpu-baseline > $OUT/${name}_${v}_$rep.log 2>&1
       elif [ "$OPT" = opts ]; then
         oa=""; [ "$v" != base ] && for kv in ${v//,/ }; do oa="$oa --opt $kv"; done
-        timeout -k 10 300 python3 bench.py $args --no-cpu-baseline $oa > $OUT/${name}_${v}_$rep.log 2>&1
+        timeout -k 10 300 python3 bench.py $args --full --no-cpu-baseline $oa > $OUT/${name}_${v}_$rep.log 2>&1
       else
-        timeout -k 10 300 python3 bench.py $args --no-cpu-baseline --opt $OPT=$v > $OUT/${name}_${v}_$rep.log 2>&1
+        timeout -k 10 300 python3 bench.py $args --full --no-cpu-baseline --opt $OPT=$v > $OUT/${name}_${v}_$rep.log 2>&1
       fi
       rc=$?
       if [ $rc -ne 0 ]; then echo "$name $v rc=$rc"; tail -5 $OUT/${name}_${v}_$rep.log; exit $rc; fi

@@ -23,10 +23,10 @@ for spec in ${CONFIGS:-C2:sah C3:sah C4:sah C2:lbvh C5:lbvh:rebuild C5:lbvh}; do
   args="--config $cfg --build $build ${rb:+--rebuild}"
   steps=100; [ "$cfg" = C3 ] && steps=40; [ "$cfg" = C5 ] && steps=12
   cpu="--no-cpu-baseline"; [ "$tag" = C2_sah ] && cpu=""
-  run "bench_$tag" 600 python3 bench.py $args --steps $steps $cpu
-  run "serial_$tag" 600 python3 bench.py $args --overlap 1 --steps $steps --no-cpu-baseline
+  run "bench_$tag" 600 python3 bench.py --full $args --steps $steps $cpu
+  run "serial_$tag" 600 python3 bench.py --full $args --overlap 1 --steps $steps --no-cpu-baseline
   run "kstats_$tag" 600 rocprofv3 --kernel-trace --stats -d "$OUT/kstats_$tag" -o run --output-format csv -- \
-      python3 bench.py $args --overlap 1 --steps $steps --no-cpu-baseline
+      python3 bench.py --full $args --overlap 1 --steps $steps --no-cpu-baseline
   run "pmc_$tag" 900 bash scripts/pmc_tagged.sh "$OUT/pmc_$tag" -- $args
 done
 exit 0

@@ -26,16 +26,16 @@ for spec in ${CONFIGS:-C2:sah C3:sah C4:sah C2:lbvh C5:lbvh:rebuild C5:lbvh}; do
   steps=100; [ "$cfg" = C3 ] && steps=40; [ "$cfg" = C5 ] && steps=12
   cpu="--no-cpu-baseline"; [ "$tag" = C2_sah ] && cpu=""
   deep=""; case "$tag" in C2_sah|C3_sah|C5_lbvh) deep=deep;; esac
-  run "bench_$tag" 600 python3 bench.py $args --steps $steps $cpu
-  run "serial_$tag" 600 python3 bench.py $args --overlap 1 --steps $steps --no-cpu-baseline
+  run "bench_$tag" 600 python3 bench.py --full $args --steps $steps $cpu
+  run "serial_$tag" 600 python3 bench.py --full $args --overlap 1 --steps $steps --no-cpu-baseline
   run "kstats_$tag" 600 rocprofv3 --kernel-trace --stats -d "$OUT/kstats_$tag" -o run --output-format csv -- \
-      python3 bench.py $args --overlap 1 --steps $steps --no-cpu-baseline
+      python3 bench.py --full $args --overlap 1 --steps $steps --no-cpu-baseline
   find "$OUT/kstats_$tag" -name '*kernel_trace.csv' -delete
   PMC_SET=$deep PMC_STEPS=$([ "$cfg" = C5 ] && echo 3 || echo 5) run "pmc_$tag" 900 bash scripts/pmc_tagged.sh "$OUT/pmc_$tag" -- $args
   rm -rf "$OUT"/pmc_$tag/pass*/
 done
 if [ -z "$NO_DRIVER" ]; then
-  run bench_driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5
-  run bench_share8 300 python3 bench.py --steps 100 --shard 0/8 --no-cpu-baseline
+  run bench_driver 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5
+  run bench_share8 300 python3 bench.py --full --steps 100 --shard 0/8 --no-cpu-baseline
 fi
 exit 0

@@ -25,10 +25,10 @@ config() {  # spec = cfg:build[:rebuild]
   steps=100; [ "$cfg" = C3 ] && steps=40; [ "$cfg" = C5 ] && steps=12
   cpu="--no-cpu-baseline"; [ "$tag" = C2_sah ] && cpu=""
   deep=""; case "$tag" in C2_sah|C3_sah|C5_lbvh) deep=deep;; esac
-  run "bench_$tag" 600 python3 bench.py $args --steps $steps $cpu
-  run "serial_$tag" 600 python3 bench.py $args --overlap 1 --steps $steps --no-cpu-baseline --no-rebuild-roofline
+  run "bench_$tag" 600 python3 bench.py --full $args --steps $steps $cpu
+  run "serial_$tag" 600 python3 bench.py --full $args --overlap 1 --steps $steps --no-cpu-baseline --no-rebuild-roofline
   run "kstats_$tag" 600 rocprofv3 --kernel-trace --stats -d "$OUT/kstats_$tag" -o run --output-format csv -- \
-      python3 bench.py $args --overlap 1 --steps $steps --no-cpu-baseline --no-rebuild-roofline
+      python3 bench.py --full $args --overlap 1 --steps $steps --no-cpu-baseline --no-rebuild-roofline
   find "$OUT/kstats_$tag" -name '*kernel_trace.csv' -delete
   PMC_SET=$deep PMC_STEPS=$([ "$cfg" = C5 ] && echo 3 || echo 5) run "pmc_$tag" 900 bash scripts/pmc_tagged.sh "$OUT/pmc_$tag" -- $args
   rm -rf "$OUT"/pmc_$tag/pass*/
@@ -39,8 +39,8 @@ if [ "${PART:-1}" = 1 ]; then
   for spec in ${CONFIGS:-C2:sah C3:sah C4:sah}; do config $spec; done
 else
   for spec in ${CONFIGS:-C2:lbvh C5:lbvh:rebuild C5:lbvh}; do config $spec; done
-  run bench_driver 300 python3 bench.py --gpus 1 --steps 20 --warmup 5
-  run bench_share8 300 python3 bench.py --steps 100 --shard 0/8 --no-cpu-baseline
-  run bench_share8_c5_rebuild 300 python3 bench.py --config C5 --build lbvh --rebuild --shard 0/8 --steps 24 --no-cpu-baseline
+  run bench_driver 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5
+  run bench_share8 300 python3 bench.py --full --steps 100 --shard 0/8 --no-cpu-baseline
+  run bench_share8_c5_rebuild 300 python3 bench.py --full --config C5 --build lbvh --rebuild --shard 0/8 --steps 24 --no-cpu-baseline
 fi
 exit 0

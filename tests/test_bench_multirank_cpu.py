@@ -5,7 +5,8 @@ GPU-facing pieces replaced inside each process: the process group is gloo instea
 no-ops, "cuda" tensors are CPU tensors, and rtamd.Renderer is a stand-in that returns fixed per-frame work.  What runs
 for real is bench.py's own multi-rank code: the RCCL id broadcast (broadcast_object_list), the clock warm-up's
 stop broadcast, the barriers, the max-over-ranks elapsed time and the summed rays (all_reduce), the hardware-queue
-override, and rank 0's single JSON line.  The library's own world > 1 frame (tiles, RCCL gather, assemble) is
+override, and rank 0's single JSON line — with --full (the passes after the timed region and their barriers) and as a
+plain run that ends after the timed steps and writes --dump-outputs.  The library's own world > 1 frame (tiles, RCCL gather, assemble) is
 covered on the GPU by tests/test_gpu_fake_rccl.py.
 """
 import json
@@ -91,18 +92,18 @@ class FakeRenderer:
 
 rtamd.Renderer = FakeRenderer
 sys.argv = ["bench.py", "--gpus", os.environ["WORLD_SIZE"], "--steps", "6", "--warmup", "2", "--clock-warmup", "0.05",
-            "--no-cpu-baseline"]
+            "--no-cpu-baseline"] + {extra!r}
 import bench
 bench.main()
 print("RANK_DONE", os.environ["RANK"], os.environ["GPU_MAX_HW_QUEUES"], flush=True)
 '''
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_bench_multirank_control_flow_gloo(tmp_path, world):
+def run_ranks(tmp_path, world, extra, port):
+    """Rank 0..world-1 of bench.py with `extra` arguments; every rank's output, rank 0's JSON line parsed."""
     script = tmp_path / "rank_main.py"
-    script.write_text(RANK_MAIN.format(repo=REPO))
-    port = str(29600 + world)
+    script.write_text(RANK_MAIN.format(repo=REPO, extra=list(extra)))
+    port = str(port)
     procs = []
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
@@ -117,7 +118,10 @@ def test_bench_multirank_control_flow_gloo(tmp_path, world):
         assert p.returncode == 0, out[-3000:]
     lines = [ln for ln in outs[0].splitlines() if ln.startswith("{")]
     assert len(lines) == 1, outs[0][-2000:]                        # rank 0 prints exactly one JSON line
-    d = json.loads(lines[0])
+    return outs, json.loads(lines[0])
+
+
+def check_line_and_ranks(d, outs, world):
     assert d["n_gpus"] == world and d["steps"] == 6 and d["warmup"] == 2
     # value = the rays of every rank's timed frames (summed over ranks) over the slowest rank's time
     rays = sum(1000 + 10 * r for r in range(world)) * 6
@@ -129,3 +133,29 @@ def test_bench_multirank_control_flow_gloo(tmp_path, world):
     for r, out in enumerate(outs):
         done = [ln.split() for ln in out.splitlines() if ln.startswith("RANK_DONE")]
         assert done and done[0][1] == str(r) and done[0][2] == "24", out[-1500:]   # N > 1: 24 hardware queues
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_bench_multirank_control_flow_gloo(tmp_path, world):
+    """--full: the passes after the timed region (serialised launches, latency frames, work counting) and their barriers."""
+    outs, d = run_ranks(tmp_path, world, ["--full"], 29600 + world)
+    check_line_and_ranks(d, outs, world)
+    assert d["full"] is True and d["roofline"]["work_per_launch"]["rays"] == 1000    # rank 0's counted share
+    assert d["frame_latency_ms_median"] > 0 and d["kernel_ms"] == pytest.approx(0.1)
+
+
+def test_bench_plain_run_multirank_gloo(tmp_path):
+    """A plain run (no --full) ends after the timed steps: the same headline fields, none of --full's blocks, and
+    --dump-outputs leaves rank 0's frame of the last timed step as float32 [pixels, 4]."""
+    import numpy as np
+    dump = tmp_path / "dump"
+    outs, d = run_ranks(tmp_path, 2, ["--dump-outputs", str(dump)], 29610)
+    check_line_and_ranks(d, outs, 2)
+    assert d["full"] is False
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    for k in ("roofline", "cpu_baseline", "frame_latency_ms_median", "kernel_ms", "rebuild"):
+        assert k not in d
+    assert sorted(os.listdir(dump)) == ["frame_rgba8.npy"]
+    a = np.load(dump / "frame_rgba8.npy")
+    assert a.dtype == np.float32 and a.shape == (1920 * 1080, 4)
