@@ -30,8 +30,9 @@ extern "C" {
 
 /* 2: rt_stats gained update_wait_ms; rt_comm_* / rt_slab_tiles / rt_tile_pixels / rt_scene_detach_comm;
  *    rt_camera_move / rt_frame_pacer_* / rt_comm_set_timeout (round 3)
- * 3: rt_scene_info gained overlap_lanes / stage_depth; "overlap" -1 = library-picked lanes on library streams */
-#define RT_ABI_VERSION 3u
+ * 3: rt_scene_info gained overlap_lanes / stage_depth; "overlap" -1 = library-picked lanes on library streams
+ * 4: rt_query_rays */
+#define RT_ABI_VERSION 4u
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -307,6 +308,63 @@ rt_status rt_tile_pixels(uint32_t width, uint32_t height, uint32_t tile_w, uint3
  * RT_ERR_STATE after rt_scene_update_triangles until a frame has run its update. */
 rt_status rt_trace_rays(rt_scene *scene, const float *rays_host, size_t ray_count,
                         uint32_t flags, rt_hit *hits_host);
+
+/* Ray queries: closest hit or occlusion for rays the caller holds in device memory, traced on the caller's
+ * stream by the render kernel's traversal (persistent waves, quad trees, the scene region in LDS; csrc/ray_query.hpp).
+ * The query reads the scene as of the last frame update (rt_scene_update, or rt_render without
+ * RT_RENDER_SKIP_UPDATE), on every build mode and option rt_trace_rays works on.
+ *
+ * Rays     : 6 floats per ray, origin xyz then direction xyz, used as given (not normalised), like rt_trace_rays.
+ * Range    : [0.001, tmax[i]] with the reference's range test (Range.cuh:33-43) — the traversal starts with
+ *            currentRange.max = tmax[i] instead of +inf.  tmax_device NULL means +inf for every ray.  A ray with
+ *            !(tmax > 0.001), NaN included, is a miss and is not traversed.  There is no per-ray tmin: the lower bound
+ *            is the render kernel's constant, and a per-ray value would have to pass through every shared box and
+ *            primitive test of that kernel, whose register budget is tight.  Start occlusion rays on a surface as the
+ *            renderer starts its bounces: from the hit point, hits nearer than 0.001 are ignored.
+ * Closest  : (RT_QUERY_ANY_HIT clear) at least one of hits_device / t_device; occluded_device must be NULL.
+ *            hits_device[i] is exactly the record rt_trace_rays writes — a miss is t = +inf, instance 0xFFFFFFFF and
+ *            every other field 0; t_device[i] = the hit's t, +inf on a miss.  With t_device alone the hit point,
+ *            normal and material are never computed.
+ * Any-hit  : (RT_QUERY_ANY_HIT) occluded_device[i] = 1 when anything lies in the ray's range, else 0; hits_device and
+ *            t_device must be NULL.  The traversal stops at the first accepted hit; it is a prefix of the closest
+ *            traversal, so a ray is occluded exactly when the closest query with the same flags finds a hit.
+ * Flags    : RT_QUERY_EXACT selects the EXACT build's arithmetic and visit order (as RT_RENDER_EXACT); otherwise the FAST
+ *            kernel of the scene's kind runs (option "fast_math" included).
+ * Ordering : the launch is enqueued on `stream` (NULL: the scene's stream, ordered with the caller's null-stream work
+ *            before and after the call as rt_render orders device outputs).  It waits for what it reads — the upload
+ *            or GPU build of the last update's frame block and a BLAS build still running — for the scene's most
+ *            recent launch and the last launch that read that frame block, and for the scene's previous query; with
+ *            "overlap" it does not wait for the other lanes' frames.  Every later upload
+ *            into a frame block and every later BLAS rebuild waits for the queries still in flight, so frames and
+ *            queries may be enqueued back to back without host synchronisation.  Without RT_QUERY_NO_SYNC the call
+ *            returns once the outputs are complete; with it, it returns after the enqueue: the outputs are ordered
+ *            on `stream`, and rt_synchronize and rt_scene_destroy wait for every query.  Queries of one scene run
+ *            in the order of their calls, whatever streams they are given and whatever frames lie between them.
+ * Errors   : RT_ERR_INVALID_ARGUMENT for reserved != 0, unknown flags, ray_count > 0xFFFFFFFF, an output combination
+ *            the mode does not allow, or a buffer that hipPointerGetAttributes does not report as accessible from the
+ *            scene's device — all before anything is enqueued; RT_ERR_STATE before rt_scene_build and after
+ *            rt_scene_update_triangles until a frame has run its update.  ray_count == 0 returns RT_OK and launches
+ *            nothing.  The caller's current device is preserved.  Allowed while a communicator is attached: the query
+ *            is local to this rank and launches no RCCL work. */
+typedef enum rt_query_flags {
+    RT_QUERY_EXACT   = 1u << 0,  /* the EXACT build's arithmetic and visit order (as RT_RENDER_EXACT) */
+    RT_QUERY_ANY_HIT = 1u << 1,  /* occlusion: stop at the first accepted hit */
+    RT_QUERY_NO_SYNC = 1u << 2   /* return after enqueue */
+} rt_query_flags;
+
+typedef struct rt_ray_query {
+    const float *rays_device;    /* 6 floats per ray: origin xyz, direction xyz (used as given, like rt_trace_rays) */
+    const float *tmax_device;    /* optional, 1 float per ray: range [0.001, tmax]; NULL = +inf */
+    uint64_t ray_count;          /* <= 0xFFFFFFFF */
+    uint32_t flags;
+    uint32_t reserved;           /* 0 */
+    rt_hit  *hits_device;        /* closest: optional; exactly the records rt_trace_rays writes (misses included) */
+    float   *t_device;           /* closest: optional; t per ray, +inf on a miss */
+    uint8_t *occluded_device;    /* any-hit: 1 / 0 per ray */
+    void    *stream;             /* hipStream_t; NULL = the scene's stream, ordered with the null stream as rt_render documents */
+} rt_ray_query;
+
+rt_status rt_query_rays(rt_scene *scene, const rt_ray_query *query);
 
 /* The box decisions of the trace kernels on caller data, for parity tests (no scene needed): box i =
  * {xmin, xmax, ymin, ymax, zmin, zmax} (6 floats), ray i = origin xyz, direction xyz, range [0.001, tmax[i]].

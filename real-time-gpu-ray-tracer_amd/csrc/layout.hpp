@@ -260,6 +260,18 @@ struct OutputGPU {
     uint32_t *unit_cost;
     uint32_t leaf_early;            // setting "leaf_early": interior loop ends with <= this many lanes still descending
 };
+// rt_query_rays (ray_query.hpp): the caller's device buffers and the call's work-queue head
+struct RayQueryGPU {
+    const float *rays;              // 6 floats per ray
+    const float *tmax;              // optional: 1 float per ray (null = +inf)
+    uint32_t n;
+    rt_hit *hits;                   // closest: optional records
+    float *t;                       // closest: optional t (+inf on a miss)
+    uint8_t *occluded;              // any-hit: 1 / 0
+    uint32_t *head;                 // QUERY_PARTS band heads, QUEUE_STRIDE words apart: chunks of 64 rays claimed so
+                                    // far in each band (zeroed before the launch)
+};
+constexpr uint32_t QUERY_PARTS = 8;           // bands of a query's chunks, one per XCD (as the frame's queue_parts)
 constexpr uint32_t QUEUE_STRIDE = 32;         // u32 words between partition heads (128 B lines)
 constexpr uint32_t QUEUE_MAX_PARTS = 8;
 // queue block of a lane: band heads (lines 0..7), band item counts (lines 8..15)

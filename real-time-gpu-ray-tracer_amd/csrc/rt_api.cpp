@@ -53,6 +53,9 @@ hipError_t launch_trace_rays_fastmath(const SceneGPU &, const float *, uint32_t,
 hipError_t launch_render_persistent_fastmath(const SceneGPU &, const CameraGPU &, const OutputGPU &, bool, unsigned long long *,
                                              uint32_t *, uint32_t, uint32_t, bool, hipStream_t);
 uint32_t persistent_blocks_per_cu_fastmath(uint32_t wide, bool raw);
+hipError_t launch_ray_query_exact(const SceneGPU &, const RayQueryGPU &, bool, uint32_t, hipStream_t);
+hipError_t launch_ray_query_fast(const SceneGPU &, const RayQueryGPU &, bool, uint32_t, hipStream_t);
+hipError_t launch_ray_query_fastmath(const SceneGPU &, const RayQueryGPU &, bool, uint32_t, hipStream_t);
 hipError_t launch_box_test_exact(const float *, const float *, const float *, uint32_t, uint32_t, uint8_t *, float *, hipStream_t);
 hipError_t launch_box_test_fast(const float *, const float *, const float *, uint32_t, uint32_t, uint8_t *, float *, hipStream_t);
 }  // namespace rtamd
@@ -261,6 +264,18 @@ struct rt_scene {
     hipEvent_t r_copied[NLANE] = {}, r_used[NLANE] = {}, r_lane[NLANE] = {};
     hipEvent_t r_done = nullptr;
     int active = -1;
+    // rt_query_rays: NQUERY slots, taken in turn, of QUERY_PARTS work-queue heads (a 128 B line each) and one completion event.
+    // A call's stream first waits on its slot's event — the query that used the slot NQUERY calls ago — so a head is
+    // never shared by two queries in flight — and on the previous call's, so queries run in call order.  A frame launch
+    // may replace r_used / r_done without having waited for a query on a caller stream, so everything that must see
+    // every query — drain, the destructor, uploads into a frame block, BLAS rebuilds, rt_scene_update_triangles' copy
+    // into raw_tris — waits on these events
+    // themselves (wait_queries), not only on the r_* pointers a query sets.
+    static constexpr uint32_t NQUERY = 8;
+    uint32_t *query_heads = nullptr;              // NQUERY x QUERY_PARTS x QUEUE_STRIDE words, allocated with the first build
+    hipEvent_t ev_query[NQUERY] = {};
+    uint32_t query_next = 0;
+    bool query_live = false;                      // a query was enqueued since every ev_query was last seen complete
 
     hipStream_t stream = nullptr;
     // per-frame kernel timing ring for pipelined frames (rt_scene_collect)
@@ -461,6 +476,8 @@ struct rt_scene {
         for (int q = 0; q < NLANE; q++)          // launches still running on caller streams
             if (r_lane[q]) (void)hipEventSynchronize(r_lane[q]);
         if (r_done) (void)hipEventSynchronize(r_done);
+        for (hipEvent_t e : ev_query)            // ray queries still running on caller streams
+            if (e) (void)hipEventSynchronize(e);
         release_comm();
         blas_pairs.release(); blas_quads.release(); tri_hot.release(); tri_cold.release(); sph_hot.release(); sph_cold.release();
         quad_hot.release(); quad_cold.release(); materials.release(); out_rgba.release(); out_rgb.release();
@@ -489,6 +506,9 @@ struct rt_scene {
             if (ev_used[b]) (void)hipEventDestroy(ev_used[b]);
         }
         if (counters) (void)hipFree(counters);
+        if (query_heads) (void)hipFree(query_heads);
+        for (hipEvent_t e : ev_query)
+            if (e) (void)hipEventDestroy(e);
         for (int q = 0; q < NLANE; q++) {
             if (queue[q]) (void)hipFree(queue[q]);
             if (ev_lane_done[q]) (void)hipEventDestroy(ev_lane_done[q]);
@@ -608,6 +628,28 @@ rt_status drain(rt_scene *s) {
     if (s->stream) RT_TRY(wait_stream(s, s->stream));
     for (int q = 0; q < rt_scene::NLANE; q++)
         if (s->r_lane[q]) RT_TRY(wait_event(s, s->r_lane[q]));
+    if (s->r_done) RT_TRY(wait_event(s, s->r_done));
+    if (s->query_live) {                                  // ray queries on caller streams
+        for (hipEvent_t e : s->ev_query)
+            if (e) RT_TRY(wait_event(s, e));
+        s->query_live = false;
+    }
+    return RT_OK;
+}
+
+// Order stream `st` after every ray query still in flight (rt_query_rays; a finished one needs no wait: a host query).
+rt_status wait_queries(rt_scene *s, hipStream_t st) {
+    if (!s->query_live) return RT_OK;                      // no query since all were last seen complete: no host work
+    bool live = false;
+    for (hipEvent_t e : s->ev_query) {
+        if (!e) continue;
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) continue;
+        if (q != hipErrorNotReady) return fail(RT_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(q));
+        HIP_TRY(hipStreamWaitEvent(st, e, 0));
+        live = true;
+    }
+    s->query_live = live;
     return RT_OK;
 }
 
@@ -719,6 +761,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
         // builds nothing would otherwise read them mid-build (rt_scene_update_triangles once, a group break)
         if (cs != s->stream && s->blas_build_seq != 0) RT_TRY(wait_blas_built(s, cs));
         if (s->r_used[b]) HIP_TRY(hipStreamWaitEvent(cs, s->r_used[b], 0));      // block b no longer read
+        RT_TRY(wait_queries(s, cs));
         // Instance::updateTransformArguments for every record of block b, on the GPU, with its BLAS root
         // (instances.hip); the deltas are read from the pinned staging block directly
         HIP_TRY(launch_instance_update(reinterpret_cast<const InstDelta *>(s->staging_dev[si] + s->off_delta), nd,
@@ -836,6 +879,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
     // went through an SDMA engine whose first use stalled a frame by ~7.6 ms; enqueued on the trace's
     // stream it is a ~4 us blit kernel between two traces.
     HIP_TRY(hipStreamWaitEvent(upload, s->r_used[b], 0));            // frame_dev[b] free on device
+    RT_TRY(wait_queries(s, upload));
     if (defer) {
         s->pending_copy = b;
         s->pending_stage = si;
@@ -1042,6 +1086,7 @@ rt_status gpu_build_blas(rt_scene *s) {
         }
         for (int q = 0; q < rt_scene::NLANE; q++)      // created with the first set (gpu_setup_blas); never recorded: no wait
             HIP_TRY(hipStreamWaitEvent(s->stream, sp.ev_lane[q], 0));
+        RT_TRY(wait_queries(s, s->stream));            // a frame on the lane may have re-recorded a query's reader event
         const RawPrimsGPU raw{s->raw_tris.p, s->raw_verts.p, s->raw_sph.p, s->raw_quad.p, (uint32_t)s->roughs.size()};
         const PrimOutGPU out{sp.tri_hot.p, s->raw_shading() ? nullptr : sp.tri_cold.p, sp.sph_hot.p, sp.sph_cold.p,
                              sp.quad_hot.p, sp.quad_cold.p};
@@ -1063,6 +1108,7 @@ rt_status gpu_build_blas(rt_scene *s) {
     if (s->blas_builds && s->r_done) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_done, 0));
     for (int q = 0; q < rt_scene::NLANE; q++)           // "overlap": the other lane's trace may still be running
         if (s->blas_builds && s->r_lane[q]) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_lane[q], 0));
+    RT_TRY(wait_queries(s, s->stream));                 // ray queries on caller streams
     const RawPrimsGPU raw{s->raw_tris.p, s->raw_verts.p, s->raw_sph.p, s->raw_quad.p, (uint32_t)s->roughs.size()};
     const PrimOutGPU out{s->tri_hot.p, s->raw_shading() ? nullptr : s->tri_cold.p, s->sph_hot.p, s->sph_cold.p,
                          s->quad_hot.p, s->quad_cold.p};
@@ -1528,6 +1574,11 @@ rt_status rt_scene_build(rt_scene *s, rt_build_mode mode, uint64_t seed) {
             const long v = std::strtol(t, nullptr, 10);
             if (v >= 1 && v <= 64) s->threshold = (uint32_t)v;
         }
+    }
+    if (!s->query_heads) {
+        HIP_TRY(hipMalloc(&s->query_heads, rt_scene::NQUERY * QUERY_PARTS * QUEUE_STRIDE * sizeof(uint32_t)));
+        HIP_TRY(hipMemset(s->query_heads, 0, rt_scene::NQUERY * QUERY_PARTS * QUEUE_STRIDE * sizeof(uint32_t)));
+        for (hipEvent_t &e : s->ev_query) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     if (!s->counters_host)
         HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->counters_host), rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long),
@@ -2100,6 +2151,105 @@ rt_status rt_trace_rays(rt_scene *s, const float *rays, size_t n, uint32_t flags
     return RT_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// the caller's current device, put back on every return path of a call that switches to the scene's
+struct DeviceRestore {
+    int prev = -1;
+    DeviceRestore() { if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); } }
+    ~DeviceRestore() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// a caller buffer kernels on `device` may touch: device memory of that device, managed memory, or mapped host memory
+bool device_accessible(const void *p, int device) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();               // an unregistered host pointer is an error of the query, not of the runtime
+        return false;
+    }
+    if (a.type == hipMemoryTypeDevice) return a.device == device;
+    if (a.type == hipMemoryTypeManaged) return true;
+    if (a.type == hipMemoryTypeHost) return a.devicePointer != nullptr;
+    return false;
+}
+}  // namespace
+
+extern "C" {
+
+rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
+    if (!s || !qy) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    const uint32_t known = RT_QUERY_EXACT | RT_QUERY_ANY_HIT | RT_QUERY_NO_SYNC;
+    if (qy->reserved != 0 || (qy->flags & ~known)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_rays: reserved bits set");
+    if (qy->ray_count > 0xFFFFFFFFull) return fail(RT_ERR_INVALID_ARGUMENT, "too many rays");
+    const bool any = (qy->flags & RT_QUERY_ANY_HIT) != 0;
+    if (any && (!qy->occluded_device || qy->hits_device || qy->t_device))
+        return fail(RT_ERR_INVALID_ARGUMENT, "an any-hit query writes occluded_device only");
+    if (!any && (qy->occluded_device || (!qy->hits_device && !qy->t_device)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "a closest query writes hits_device and / or t_device");
+    if (qy->ray_count && !qy->rays_device) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
+    if (qy->ray_count == 0) return RT_OK;
+    if (s->blas_dirty)
+        return fail(RT_ERR_STATE, "triangles were updated since the last frame update: render a frame with the update first");
+    DeviceRestore restore;
+    HIP_TRY(hipSetDevice(s->device));
+    const void *bufs[] = {qy->rays_device, qy->tmax_device, qy->hits_device, qy->t_device, qy->occluded_device};
+    for (const void *p : bufs)
+        if (p && !device_accessible(p, s->device))
+            return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_rays: a buffer is not accessible from the scene's device");
+
+    hipStream_t st = qy->stream ? static_cast<hipStream_t>(qy->stream) : s->stream;
+    const uint32_t slot = s->query_next;       // advanced once the query is enqueued: a failed call takes no slot
+    hipEvent_t done = s->ev_query[slot];
+    const int b = s->active;
+    // What the launch waits for.  Its slot's previous query (head free; see ev_query) and the previous call's (queries
+    // run in call order even with a frame's launch between them).  The frame block of the last
+    // update, as a RT_RENDER_SKIP_UPDATE frame does, and a GPU BLAS build still running on the scene's stream.  And
+    // every event this call replaces below — r_used[b], r_done, the BLAS set's reader event: whoever waits on those
+    // afterwards sees only this query, which runs on a caller stream and so implies nothing about the launches on the
+    // lane streams they stood for.
+    // An event that has already completed needs no wait (a host query, ~1 us, as wait_blas_built): whatever is enqueued
+    // now runs after it, and each cross-stream wait in front of a kernel costs GPU idle time.  The
+    // purposes often share one event (a frame's single completion event): each is waited on once.
+    const int bl = s->last_lane;
+    hipEvent_t prev_query = s->ev_query[(slot + rt_scene::NQUERY - 1) % rt_scene::NQUERY];
+    hipEvent_t deps[] = {done, prev_query, s->r_copied[b], s->r_used[b], s->r_done, s->ev_blas_lane[bl]};
+    for (size_t i = 0; i < sizeof deps / sizeof deps[0]; i++) {
+        bool dup = !deps[i];
+        for (size_t j = 0; j < i && !dup; j++) dup = deps[j] == deps[i];
+        if (dup) continue;
+        const hipError_t qe = hipEventQuery(deps[i]);
+        if (qe == hipSuccess) continue;
+        if (qe != hipErrorNotReady) return fail(RT_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(qe));
+        HIP_TRY(hipStreamWaitEvent(st, deps[i], 0));
+    }
+    if (!qy->stream && hipStreamQuery(nullptr) == hipErrorNotReady) {      // the caller's null-stream work (rt_render)
+        if (!s->ev_caller) HIP_TRY(hipEventCreateWithFlags(&s->ev_caller, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(s->ev_caller, nullptr));
+        HIP_TRY(hipStreamWaitEvent(st, s->ev_caller, 0));
+    }
+    if (s->blas_build_seq != 0 && st != s->stream) RT_TRY(wait_blas_built(s, st));
+
+    const SceneGPU g = scene_gpu(s);
+    RayQueryGPU q{};
+    q.rays = qy->rays_device; q.tmax = qy->tmax_device;
+    q.n = (uint32_t)qy->ray_count;
+    q.hits = qy->hits_device; q.t = qy->t_device; q.occluded = qy->occluded_device;
+    q.head = s->query_heads + (size_t)slot * QUERY_PARTS * QUEUE_STRIDE;
+    HIP_TRY((qy->flags & RT_QUERY_EXACT) ? launch_ray_query_exact(g, q, any, s->cus, st)
+                                         : (s->fast_math ? launch_ray_query_fastmath(g, q, any, s->cus, st)
+                                                         : launch_ray_query_fast(g, q, any, s->cus, st)));
+    HIP_TRY(hipEventRecord(done, st));
+    s->query_next = (slot + 1) % rt_scene::NQUERY;
+    s->query_live = true;
+    s->r_used[b] = s->r_done = done;           // later uploads into block b, later BLAS rebuilds, rt_synchronize
+    if (s->ev_blas_lane[bl]) HIP_TRY(hipEventRecord(s->ev_blas_lane[bl], st));   // "blas_double": this set's reader
+    if (!qy->stream) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
+    if (qy->flags & RT_QUERY_NO_SYNC) return RT_OK;
+    return wait_event(s, done);
+}
+
 rt_status rt_box_test(int device, const float *boxes, const float *rays, const float *tmax, size_t n, uint32_t mode,
                       uint8_t *hit, float *te) {
     if (n && (!boxes || !rays || !tmax || !hit || !te)) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
@@ -2426,6 +2576,7 @@ rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, con
         if (s->r_done) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_done, 0));
         for (int q = 0; q < rt_scene::NLANE; q++)
             if (s->r_lane[q]) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_lane[q], 0));
+        RT_TRY(wait_queries(s, s->stream));          // a query's records read raw_tris too (finalize, RAW 1)
     }
     HIP_TRY(hipMemcpyAsync(s->raw_tris.p + first, s->raw_stage, count * sizeof(rt_triangle), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(extract_tri_verts(s->raw_tris.p, s->raw_verts.p, first, count, s->stream));

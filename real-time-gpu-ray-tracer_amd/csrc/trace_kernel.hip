@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "layout.hpp"
 #include "../../include/rt.h"
 
@@ -556,6 +558,22 @@ __device__ __forceinline__ void trav_init(Trav &T, const TreeRoot &R, const f3 &
 template <int XB = XD_CULL>
 __device__ __forceinline__ void trav_init(Trav &T, const SceneGPU &sc, const f3 &o, const f3 &d) {
     trav_init<XB>(T, *sc.tlas_root, o, d);
+}
+// a caller's ray with the range [TMIN, tmax] (ray_query.hpp): the traversal starts with currentRange.max = tmax
+template <int XB = XD_CULL>
+__device__ __forceinline__ void trav_init(Trav &T, const TreeRoot &R, const f3 &o, const f3 &d, float tmax) {
+    T.wr.o = o; T.wr.d = d; prep<XB>(T.wr);
+    T.lr = T.wr;
+    T.tmax = tmax;
+    T.found = false;
+    T.stk.sp = 0;
+    T.stk.spilled = 0;
+    T.cur = R.ref;
+    T.cur_inst = 0;
+    T.pleaf = REF_NONE;
+    float te = 0.0f;
+    T.tracing = slab<XB>(R.box, T.wr, TMIN, T.tmax, te);
+    T.curT = te;
 }
 
 // The frame's TLAS root as wave-uniform values (SGPRs): read once per wave instead of per ray.
@@ -1940,5 +1958,7 @@ hipError_t RT_SUFFIX(launch_box_test)(const float *boxes, const float *rays, con
     hipLaunchKernelGGL(box_test_kernel, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, boxes, rays, tmax, n, mode, hit, te);
     return hipGetLastError();
 }
+
+#include "ray_query.hpp"
 
 }  // namespace rtamd

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-RT_ABI_VERSION = 3
+RT_ABI_VERSION = 4
 
 RT_OK = 0
 RT_STATUS_NAMES = {
@@ -29,6 +29,10 @@ RT_RENDER_COUNT_WORK = 1 << 1
 RT_RENDER_NO_SYNC = 1 << 2
 RT_RENDER_SKIP_UPDATE = 1 << 3
 RT_RENDER_KEEP_COUNTERS = 1 << 4
+
+RT_QUERY_EXACT = 1 << 0
+RT_QUERY_ANY_HIT = 1 << 1
+RT_QUERY_NO_SYNC = 1 << 2
 
 MISS = 0xFFFFFFFF
 
@@ -119,6 +123,13 @@ class Hit(C.Structure):
                 ("material_type", C.c_uint32), ("material_index", C.c_uint32)]
 
 
+class RayQuery(C.Structure):
+    """rt_ray_query: device ray stream, optional per-ray tmax, outputs and stream of one rt_query_rays call."""
+    _fields_ = [("rays_device", C.c_void_p), ("tmax_device", C.c_void_p), ("ray_count", C.c_uint64),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32), ("hits_device", C.c_void_p),
+                ("t_device", C.c_void_p), ("occluded_device", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("blas_count", C.c_uint64), ("blas_node_pairs", C.c_uint64),
                 ("blas_leaves", C.c_uint64), ("tlas_node_pairs", C.c_uint64),
@@ -169,7 +180,7 @@ EXPORTED_SYMBOLS = (
     "rt_vtk_series_read", "rt_vtk_series_count", "rt_vtk_series_entry", "rt_vtk_series_free",
     "rt_comm_unique_id", "rt_scene_attach_comm", "rt_scene_detach_comm", "rt_slab_tiles", "rt_tile_pixels",
     "rt_comm_set_timeout", "rt_camera_control_init", "rt_camera_move", "rt_clock_ns", "rt_frame_pace",
-    "rt_box_test",
+    "rt_box_test", "rt_query_rays",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -197,6 +208,8 @@ def _declare(lib):
     lib.rt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, P(Hit)]
     lib.rt_box_test.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.rt_box_test.restype = C.c_int
+    lib.rt_query_rays.argtypes = [C.c_void_p, P(RayQuery)]
+    lib.rt_query_rays.restype = C.c_int
     lib.rt_synchronize.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.restype = None

@@ -12,10 +12,22 @@ There is no CPU fallback: constructing a Renderer without librtamd.so or without
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import nullcontext as _null_context
 
 import numpy as np
 
 from . import abi
+
+HIT_DTYPE = np.dtype([("t", np.float32), ("instance", np.uint32), ("ptype", np.uint32),
+                      ("pindex", np.uint32), ("point", np.float32, 3), ("normal", np.float32, 3),
+                      ("mtype", np.uint32), ("midx", np.uint32)])     # rt_hit, as Renderer.trace_rays returns it
+
+
+def hits_to_numpy(hits) -> np.ndarray:
+    """The rt_hit records of Renderer.query_rays (torch uint8 [N, 48], any device) as the structured array
+    Renderer.trace_rays returns."""
+    raw = hits.detach().cpu().numpy() if hasattr(hits, "detach") else np.asarray(hits, np.uint8)
+    return np.ascontiguousarray(raw).reshape(-1, HIT_DTYPE.itemsize).view(HIT_DTYPE).reshape(-1).copy()
 
 
 class Renderer:
@@ -201,6 +213,73 @@ class Renderer:
                                  ("mtype", np.uint32), ("midx", np.uint32)])
         out[:] = np.frombuffer(hits, dtype=out.dtype, count=n)
         return out
+
+    def query_rays(self, rays, tmax=None, *, any_hit: bool = False, exact: bool = False, want_hits: bool = True,
+                   stream=None, sync: bool = True):
+        """rt_query_rays on device tensors: rays [N, 6] (origin, direction) and optional tmax [N] (range
+        [0.001, tmax], None = +inf) as torch CUDA float32 tensors on the scene's device (numpy arrays are uploaded
+        through torch).  stream: a torch.cuda.Stream or a raw hipStream_t (None = torch's current stream).
+        Closest mode returns (t float32 [N] with +inf on a miss, hits uint8 [N, 48] rt_hit records — see
+        hits_to_numpy — or None without want_hits); any_hit returns occluded bool [N].  With sync=False the call
+        returns after the enqueue and the tensors are valid in stream order."""
+        import torch                              # here: `import rtamd` needs no torch
+
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        # uploads and outputs are made on the query's stream, so they are ordered with the launch and torch's
+        # allocator orders their reuse with it.  A raw hipStream_t gives torch nothing to order with: a numpy input's
+        # upload is then waited for, and the call waits for the query before the temporary is released.
+        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+        uploaded = []
+
+        def device_f32(x, shape, name):
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(np.ascontiguousarray(x, np.float32)).to(dev)
+                uploaded.append(x)
+            if not isinstance(x, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor or a numpy array")
+            if x.dtype != torch.float32:
+                raise ValueError(f"{name}: float32, not {x.dtype}")
+            if x.device != dev:
+                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+            if tuple(x.shape[1:]) != shape or x.dim() != 1 + len(shape):
+                raise ValueError(f"{name}: shape [N{''.join(', %d' % k for k in shape)}], not {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+            return x
+
+        with ctx:
+            rays = device_f32(rays, (6,), "rays")
+            n = rays.shape[0]
+            if tmax is not None:
+                tmax = device_f32(tmax, (), "tmax")
+                if tmax.shape[0] != n:
+                    raise ValueError("tmax: one value per ray")
+        if uploaded and not isinstance(stream, torch.cuda.Stream):
+            torch.cuda.current_stream(dev).synchronize()
+            sync = True
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        q = abi.RayQuery()
+        q.rays_device = rays.data_ptr() if n else None
+        q.tmax_device = tmax.data_ptr() if (tmax is not None and n) else None
+        q.ray_count = n
+        q.flags = (abi.RT_QUERY_EXACT if exact else 0) | (abi.RT_QUERY_ANY_HIT if any_hit else 0) | \
+                  (0 if sync else abi.RT_QUERY_NO_SYNC)
+        q.stream = raw or None
+        with ctx:
+            if any_hit:
+                occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+                q.occluded_device = occ.data_ptr()
+            else:
+                t = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+                hits = torch.empty((max(n, 1), C.sizeof(abi.Hit)), dtype=torch.uint8, device=dev) if want_hits else None
+                q.t_device = t.data_ptr()
+                q.hits_device = hits.data_ptr() if want_hits else None
+        abi.check(self.lib, self.lib.rt_query_rays(self.h, C.byref(q)))
+        if any_hit:
+            return occ[:n].view(torch.bool)
+        return t[:n], (hits[:n] if want_hits else None)
 
     def synchronize(self):
         abi.check(self.lib, self.lib.rt_synchronize(self.h))
