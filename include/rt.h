@@ -317,7 +317,14 @@ rt_status rt_trace_rays(rt_scene *scene, const float *rays_host, size_t ray_coun
  * Rays     : 6 floats per ray, origin xyz then direction xyz, used as given (not normalised), like rt_trace_rays.
  * Range    : [0.001, tmax[i]] with the reference's range test (Range.cuh:33-43) — the traversal starts with
  *            currentRange.max = tmax[i] instead of +inf.  tmax_device NULL means +inf for every ray.  A ray with
- *            !(tmax > 0.001), NaN included, is a miss and is not traversed.  There is no per-ray tmin: the lower bound
+ *            !(tmax > 0.001), NaN included, is a miss and is not traversed.  As in the reference the two ends of the
+ *            test differ between primitives and boxes: a primitive's t is accepted when |t - tmax| < 1e-6 or
+ *            0.001 < t < tmax, but a box is left out once its entry t >= tmax (BoundingBox.cu:34-72).  So tmax = t of
+ *            a known hit, or one ulp above it, finds that hit again except where the surface touches a face of a box
+ *            around it and the box's entry t rounds to t or above (the ground sphere's top under its box's top, the
+ *            parallelogram in its q-centred box: 29 of 15 003 hits on the ray-query test scene); which boxes lie
+ *            around a surface depends on the build mode.  Pass a bound with slack (the occlusion radius, 2 t) where
+ *            the hit must be kept.  There is no per-ray tmin: the lower bound
  *            is the render kernel's constant, and a per-ray value would have to pass through every shared box and
  *            primitive test of that kernel, whose register budget is tight.  Start occlusion rays on a surface as the
  *            renderer starts its bounces: from the hit point, hits nearer than 0.001 are ignored.

@@ -47,6 +47,8 @@ def lib():
         L.oracle_render.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(Counters)]
         L.oracle_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, P(abi.Hit), C.c_int, P(Counters)]
+        L.oracle_trace_range.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, P(abi.Hit), C.c_int,
+                                         P(Counters)]
         for n in ("oracle_export_blas",):
             getattr(L, n).argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       P(C.c_uint32), P(C.c_uint32)]
@@ -129,12 +131,19 @@ class OracleScene:
         assert rc == 0, rc
         return rgb, rgba, cnt.as_dict()
 
-    def trace(self, rays, brute_force: bool = False):
+    def trace(self, rays, brute_force: bool = False, tmax=None):
+        """Closest hits over [0.001, tmax[i]] (tmax=None: +inf) with the reference's range test."""
         rays = _f32(rays).reshape(-1, 6)
         n = rays.shape[0]
         hits = (self._abi.Hit * max(1, n))()
         cnt = Counters()
-        assert lib().oracle_trace(self.h, rays.ctypes.data, n, hits, int(brute_force), C.byref(cnt)) == 0
+        if tmax is None:
+            assert lib().oracle_trace(self.h, rays.ctypes.data, n, hits, int(brute_force), C.byref(cnt)) == 0
+        else:
+            tmax = _f32(tmax).reshape(-1)
+            assert tmax.shape[0] == n
+            assert lib().oracle_trace_range(self.h, rays.ctypes.data, tmax.ctypes.data, n, hits, int(brute_force),
+                                            C.byref(cnt)) == 0
         return hits_to_numpy(hits, n), cnt.as_dict()
 
     def instance_state(self):

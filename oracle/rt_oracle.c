@@ -1041,17 +1041,22 @@ int oracle_render(const oracle_scene *s, uint64_t frame_seed, uint32_t x0, uint3
     return 0;
 }
 
-int oracle_trace(const oracle_scene *s, const float *rays, size_t n, rt_hit *hits, int brute, oracle_counters *counters) {
+/* oracle_trace with the initial Range {TMIN, tmax[i]} handed to tlas_hit (tmax == NULL: +inf for every ray).  A ray
+ * with !(tmax[i] > TMIN), NaN included, is a miss record and is not traversed: that is rt_query_rays' documented rule
+ * (include/rt.h, rt_ray_query.tmax_device), not the reference's, whose Range would still accept t in the 1e-6 windows
+ * around an empty or inverted interval. */
+int oracle_trace_range(const oracle_scene *s, const float *rays, const float *tmax, size_t n, rt_hit *hits, int brute,
+                       oracle_counters *counters) {
     if (!s) return 1;
     oracle_counters local; memset(&local, 0, sizeof local);
     Ctx cx = {s, &local, brute};
-    const Range range = {TMIN, INFINITY};
     for (size_t i = 0; i < n; i++) {
         Ray r; r.o = v3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]); r.d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+        const Range range = {TMIN, tmax ? tmax[i] : INFINITY};
         Hit rec; memset(&rec, 0, sizeof rec);
         rt_hit *o = &hits[i];
         memset(o, 0, sizeof *o);
-        if (tlas_hit(&cx, &r, range, &rec)) {
+        if (range.max > TMIN && tlas_hit(&cx, &r, range, &rec)) {
             o->t = rec.t; o->instance = rec.inst; o->primitive_type = rec.ptype; o->primitive_index = rec.pidx;
             o->point = tort(rec.point); o->normal = tort(rec.normal);
             o->material_type = rec.mtype; o->material_index = rec.midx;
@@ -1061,6 +1066,10 @@ int oracle_trace(const oracle_scene *s, const float *rays, size_t n, rt_hit *hit
     }
     if (counters) *counters = local;
     return 0;
+}
+
+int oracle_trace(const oracle_scene *s, const float *rays, size_t n, rt_hit *hits, int brute, oracle_counters *counters) {
+    return oracle_trace_range(s, rays, NULL, n, hits, brute, counters);
 }
 
 /* ------------------------------------------------------------------------------------

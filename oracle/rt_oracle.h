@@ -54,6 +54,11 @@ int oracle_render(const oracle_scene *s, uint64_t frame_seed,
 /* Closest hit of world rays (ox,oy,oz,dx,dy,dz per ray) over [0.001, inf). */
 int oracle_trace(const oracle_scene *s, const float *rays, size_t n, rt_hit *hits,
                  int brute_force, oracle_counters *counters);
+/* The same over [0.001, tmax[i]] per ray, with the reference's closed, +-1e-6-windowed range test at both ends
+ * (Range.cuh:33-43).  tmax == NULL is +inf.  !(tmax[i] > 0.001), NaN included, is a miss record without traversal
+ * (rt.h's rule for rt_query_rays).  TESTS ONLY: the truth for ranged ray queries. */
+int oracle_trace_range(const oracle_scene *s, const float *rays, const float *tmax, size_t n, rt_hit *hits,
+                       int brute_force, oracle_counters *counters);
 
 /* Tree export in the reference node form (for tree-identity tests). */
 int oracle_export_blas(const oracle_scene *s, uint32_t blas_index, float *node_boxes,

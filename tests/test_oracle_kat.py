@@ -308,3 +308,113 @@ def test_c1_bvh_equals_brute_force_256(oracle_lib, depth):
         if depth == 1:
             assert np.array_equal(a_rgb, b_rgb) and ca["rays"] == cb["rays"] == 256 * 256
         assert abs(ca["rays"] - cb["rays"]) <= 2
+
+
+# ---- oracle_trace_range: the truth for ranged ray queries (rt_query_rays, include/rt.h) -------------------------------
+RQ_BUILD_SEED = 9            # the ray-query scene of tests/test_gpu_ray_query.py: demo_with_particles(16), build seed 9
+
+
+@pytest.fixture(scope="module")
+def rq(oracle_lib):
+    """(oracle scene, gen_rays(20000, 4), its unbounded hits, the boundary tmax set of tests/ray_query_ref.py)."""
+    from oracle.oracle import OracleScene
+    from ray_query_ref import boundary_tmax
+    from test_gpu_ray_query import gen_rays
+    o = OracleScene(scenes.demo_with_particles(16), build_seed=RQ_BUILD_SEED)
+    rays = gen_rays(20000, 4)
+    hits = o.trace(rays)[0]
+    return o, rays, hits, boundary_tmax(hits["t"], hits["instance"] != abi.MISS)
+
+
+def _same_records(a, b):
+    for k in a.dtype.names:
+        assert np.array_equal(a[k], b[k]), (k, int((a[k] != b[k]).sum()))
+
+
+def test_trace_range_unbounded_is_oracle_trace(rq):
+    """tmax=None (oracle_trace) and an explicit all-inf array (oracle_trace_range) give the same records bit for bit,
+    and so do the counters: the ranged entry point is the same traversal."""
+    o, rays, hits, _ = rq
+    a, ca = o.trace(rays)
+    b, cb = o.trace(rays, tmax=np.full(len(rays), np.inf, np.float32))
+    assert a.tobytes() == b.tobytes() == hits.tobytes() and ca == cb
+    assert 15000 <= (a["instance"] != abi.MISS).sum() <= 15010
+
+
+def test_trace_range_empty_ranges_are_untraversed_misses(rq):
+    """rt.h: a ray with !(tmax > 0.001), NaN included, is a miss and is not traversed (no instance visited)."""
+    o, rays, _, _ = rq
+    for v in (0.001, 0.0, 0.0005, -1.0, -np.inf, np.nan):
+        h, cnt = o.trace(rays[:512], tmax=np.full(512, v, np.float32))
+        assert np.all(h["t"] == np.inf) and np.all(h["instance"] == abi.MISS), v
+        for k in ("ptype", "pindex", "mtype", "midx", "point", "normal"):
+            assert not h[k].any(), (v, k)
+        assert cnt["rays"] == 0 and cnt["aabb_tests"] == 0, v
+
+
+@pytest.mark.parametrize("case", [None, "t_c", "next_down", "next_up", "minus_5e-7", "plus_5e-7", "minus_2e-6",
+                                  "plus_2e-6"])
+def test_trace_range_tree_equals_box_gated_brute_force(rq, case):
+    """The tree path equals the loop over every instance and primitive gated by the primitive's box (brute_force=2),
+    for the first 4 000 rays of the ray-query scene: unbounded and with tmax on, one ulp off, inside and outside the
+    1e-6 window around each ray's closest hit.  The range reaches the boxes and the primitives of both paths alike."""
+    o, rays, hits, bounds = rq
+    n = 4000
+    tmax = None if case is None else bounds[case][:n]
+    tree = o.trace(rays[:n], tmax=tmax)[0]
+    brute = o.trace(rays[:n], brute_force=2, tmax=tmax)[0]
+    for k in ("t", "instance", "pindex"):
+        assert np.array_equal(tree[k], brute[k]), (k, int((tree[k] != brute[k]).sum()))
+    hit = hits["instance"][:n] != abi.MISS
+    got = tree["instance"] != abi.MISS
+    assert not got[~hit].any()                                  # a narrower range finds nothing new
+    if case is None:
+        _same_records(tree, hits[:n])
+    # (a bound just above t_c does not always keep the hit: where the ground sphere touches the top of its box the box's
+    # entry t rounds to t_c, tmax = t_c + 2e-6 rounds to t_c for t_c >= 64, and BoundingBox::hit culls at min >= max)
+    if case == "minus_5e-7":
+        assert (got & (tree["t"] > tmax)).sum() > 1000          # the window at work: t in (tmax, tmax + 1e-6)
+    if case == "minus_2e-6":
+        assert (hit & ~got).sum() > 1000 and got.sum() > 0      # beyond the window; 2e-6 below half an ulp: tmax = t_c
+
+
+@pytest.mark.parametrize("kind", ["sphere", "tri", "quad"])
+def test_trace_range_single_primitive(oracle_lib, kind):
+    """One primitive under an identity instance: the ranged trace equals the primitive's own hit function called with
+    range = {0.001, tmax}, gated by the primitive's box under the same range (the TLAS leaf, the BLAS root: the same
+    box), as tests/test_gpu_golden.py::test_prim_kats_through_trace gates it."""
+    import ctypes as C
+    import os
+    from oracle.oracle import OracleScene, lib
+    from ray_query_ref import boundary_tmax
+    from test_gpu_golden import GOLDEN, _single_prim_scene
+    prims = {"sphere": sphere((0.3, -0.2, 0.1), 1.3), "quad": quad((-1, -0.5, 0.2), (2, 0.3, 0), (0.2, 1.7, 0.4)),
+             "tri": tri((-1, -1, 0.1), (1.2, -0.8, -0.2), (0.1, 1.1, 0.3), ((0, 0, 1), (0.3, 0, 0.95), (0, 0.3, 0.95)))}
+    prim = prims[kind]
+    rays = np.ascontiguousarray(np.load(os.path.join(GOLDEN, "prim_kats.npz"))[f"{kind}_rays"], np.float32)
+    o = OracleScene(_single_prim_scene(kind, prim))
+    free = o.trace(rays)[0]
+    hit0 = free["instance"] != abi.MISS
+    assert hit0.sum() > 100
+    box = np.zeros(6, np.float32)
+    ptype = {"sphere": abi.SPHERE, "quad": abi.PARALLELOGRAM, "tri": abi.TRIANGLE}[kind]
+    lib().oracle_prim_bounds(ptype, C.byref(prim), box.ctypes.data)
+    te = np.zeros(1, np.float32)
+    bounds = boundary_tmax(free["t"], hit0)
+    bounds["half"] = np.where(hit0, 0.5 * free["t"], 10.0).astype(np.float32)
+    bounds["inf"] = np.full(len(rays), np.inf, np.float32)
+    for name, tmax in bounds.items():
+        got = o.trace(rays, tmax=tmax)[0]
+        want_hit = np.zeros(len(rays), bool)
+        want = np.zeros((len(rays), 9), np.float32)
+        for i in range(len(rays)):
+            rg = _rng(0.001, tmax[i])
+            if not lib().oracle_hit_aabb(box.ctypes.data, rays[i].ctypes.data, rg.ctypes.data, te.ctypes.data):
+                continue
+            want_hit[i], want[i] = hit(kind, prim, rays[i], (0.001, tmax[i]))
+        assert np.array_equal(got["instance"] != abi.MISS, want_hit), name
+        assert np.array_equal(got["t"][want_hit], want[want_hit, 0]), name
+        assert np.array_equal(got["point"][want_hit], want[want_hit, 1:4]), name
+        assert np.all(got["t"][~want_hit] == np.inf), name
+        if name == "half":
+            assert not want_hit.any()                           # nothing is nearer than the closest hit
