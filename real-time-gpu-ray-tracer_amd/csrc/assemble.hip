@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.hpp"
 #include "layout.hpp"
 
 namespace rtamd {

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "host_math.hpp"
+#include "launch.hpp"
 #include "layout.hpp"
 
 namespace rtamd {

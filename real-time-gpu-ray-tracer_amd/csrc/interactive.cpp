@@ -16,9 +16,8 @@
 #include <thread>
 
 #include "../../include/rt.h"
+#include "error.hpp"
 #include "host_math.hpp"
-
-void rtamd_set_error(const std::string &msg);   // rt_api.cpp
 
 using namespace rtamd::hm;
 

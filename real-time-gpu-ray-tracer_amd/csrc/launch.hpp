@@ -1,0 +1,65 @@
+// launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip) and the host files that call them
+// include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rt.h"
+#include "layout.hpp"
+
+namespace rtamd {
+
+// trace_kernel.hip, once per flavour: exact (the reference's arithmetic and traversal), fast (the default FAST kernels)
+// and fastmath (option "fast_math": the FAST kernels with hardware reciprocals and FMA contraction, trace_fastmath.o)
+#define RTAMD_TRACE_LAUNCHERS(sfx)                                                                                        \
+    hipError_t launch_render_##sfx(const SceneGPU &, const CameraGPU &, const OutputGPU &, bool, unsigned long long *,   \
+                                   hipStream_t);                                                                          \
+    hipError_t launch_render_persistent_##sfx(const SceneGPU &, const CameraGPU &, const OutputGPU &, bool,              \
+                                              unsigned long long *, uint32_t *, uint32_t, uint32_t, bool, hipStream_t);  \
+    uint32_t persistent_blocks_per_cu_##sfx(uint32_t wide, bool raw);                                                     \
+    hipError_t launch_trace_rays_##sfx(const SceneGPU &, const float *, uint32_t, rt_hit *, hipStream_t);                \
+    hipError_t launch_ray_query_##sfx(const SceneGPU &, const RayQueryGPU &, bool, uint32_t, hipStream_t);
+RTAMD_TRACE_LAUNCHERS(exact)
+RTAMD_TRACE_LAUNCHERS(fast)
+RTAMD_TRACE_LAUNCHERS(fastmath)
+#undef RTAMD_TRACE_LAUNCHERS
+// rt_box_test: the reference's slab test or the FAST one; it has no fast_math form of its own
+hipError_t launch_box_test_exact(const float *, const float *, const float *, uint32_t, uint32_t, uint8_t *, float *, hipStream_t);
+hipError_t launch_box_test_fast(const float *, const float *, const float *, uint32_t, uint32_t, uint8_t *, float *, hipStream_t);
+
+// assemble.hip, schedule.hip, instances.hip
+hipError_t launch_assemble(const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, void *, hipStream_t);
+hipError_t launch_frame_copy(void *, const void *, size_t, unsigned long long *, uint32_t *, hipStream_t);
+hipError_t launch_schedule(uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint32_t, uint32_t, uint32_t, bool, uint32_t,
+                           uint32_t, uint32_t, void *, const void *, size_t, unsigned long long *, hipStream_t);
+hipError_t launch_instance_slot_order(const uint32_t *, const InstHot *, const InstCold *, uint32_t, InstHot *, InstCold *,
+                                      hipStream_t);
+hipError_t launch_instance_update(const InstDelta *, uint32_t, InstParams *, uint32_t, InstHot *, InstCold *, float *, float4 *,
+                                  const uint32_t *, const TreeRoot *, const uint32_t *, bool, hipStream_t);
+
+// One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
+struct TraceFlavour {
+    decltype(&launch_render_exact) render;
+    decltype(&launch_render_persistent_exact) render_persistent;
+    decltype(&persistent_blocks_per_cu_exact) blocks_per_cu;
+    decltype(&launch_trace_rays_exact) trace_rays;
+    decltype(&launch_ray_query_exact) ray_query;
+};
+inline const TraceFlavour &trace_flavour(bool exact, bool fast_math) {
+#define RTAMD_FLAVOUR(sfx)                                                                                                \
+    {launch_render_##sfx, launch_render_persistent_##sfx, persistent_blocks_per_cu_##sfx, launch_trace_rays_##sfx,       \
+     launch_ray_query_##sfx}
+    static constexpr TraceFlavour table[3] = {RTAMD_FLAVOUR(exact), RTAMD_FLAVOUR(fast), RTAMD_FLAVOUR(fastmath)};
+#undef RTAMD_FLAVOUR
+    return table[exact ? 0 : (fast_math ? 2 : 1)];
+}
+// resident workgroups per CU of the flavour's persistent kernel: the EXACT kernel has one form, the FAST ones one per
+// tree form and shading source of the scene
+inline uint32_t persistent_blocks_per_cu(bool exact, bool fast_math, const SceneGPU &g) {
+    const TraceFlavour &f = trace_flavour(exact, fast_math);
+    return exact ? f.blocks_per_cu(0u, false) : f.blocks_per_cu(g.wide, g.raw_tris != nullptr);
+}
+
+}  // namespace rtamd

@@ -30,6 +30,7 @@
 
 #include <atomic>
 
+#include "launch.hpp"
 #include "layout.hpp"
 #include "../../include/rt.h"
 

@@ -36,8 +36,7 @@
 #include <vector>
 
 #include "../../include/rt.h"
-
-void rtamd_set_error(const std::string &msg);
+#include "error.hpp"
 
 namespace {
 

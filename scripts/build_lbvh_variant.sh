@@ -7,7 +7,7 @@ make -s
 NAME=$1; FLAGS=$2
 HIPCC=/opt/rocm/bin/hipcc
 $HIPCC -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -ffp-contract=off $FLAGS -c lbvh.hip -o ../build/lbvh_$NAME.o
-objs=""
-for o in rt_api trace_exact trace_fast trace_fastmath assemble schedule vtk_reader comm instances interactive; do objs="$objs ../build/$o.o"; done
+# the default library's objects (the Makefile knows them) without the one replaced here
+objs=$(make -s link-objs | tr ' ' '\n' | grep -v '/lbvh\.o$' | tr '\n' ' ')
 $HIPCC -shared -fPIC --offload-arch=gfx950 -o ../lib/librtamd_$NAME.so $objs ../build/lbvh_$NAME.o -ldl
 echo "built ../lib/librtamd_$NAME.so"

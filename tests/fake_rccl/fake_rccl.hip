@@ -1,6 +1,6 @@
 // fake_rccl.hip — a test-only stand-in for librccl.so.1 that runs an N-rank "world" inside one process on one
 // GPU, so the library's multi-GPU frame (rt_scene_attach_comm: trace -> grouped ncclSend / ncclRecv gather ->
-// assemble, csrc/rt_api.cpp) runs its world > 1 branch on a one-GPU box (verdict r3 item 2).
+// assemble, csrc/scene_comm.cpp) runs its world > 1 branch on a one-GPU box (verdict r3 item 2).
 //
 // Test infrastructure, never product: librtamd.so loads it only when RTAMD_RCCL_LIB names it (csrc/comm.cpp).
 // It implements exactly the entry points comm.hpp resolves, with the semantics the library relies on:

@@ -5,7 +5,7 @@ per process).  Every rank is a scene of its own on device 0, driven from this th
 ranks would post their work (senders first, rank 0 last, the same lane sequence on every rank).  The library's
 world > 1 branch runs as on 8 GPUs: rank r traces its interleaved tiles into its lane's slab and sends it to
 rank 0 (grouped ncclSend / ncclRecv), rank 0 receives the slabs into its lane's gather buffer and assembles the
-frame (csrc/rt_api.cpp rt_render).  Prints one JSON line per case; exits non-zero on the first failure.
+frame (csrc/render.cpp rt_render, csrc/scene_comm.cpp comm_gather).  Prints one JSON line per case; exits non-zero on the first failure.
 """
 import json
 import os

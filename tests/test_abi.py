@@ -68,6 +68,21 @@ def test_library_exports_every_declared_symbol(rtlib_path):
         assert re.search(rf"\bT {name}$", nm, re.M), name
 
 
+# unmangled text symbols the toolchain itself defines in a shared library (_init, _fini, ...): this toolchain's
+# `nm -D --defined-only` lists none as T, so none is allowed
+TOOLCHAIN_SYMBOLS = frozenset()
+
+
+def test_library_exports_only_declared_c_symbols(rtlib_path):
+    """The reverse direction: every unmangled function the library defines is one include/rt.h declares (an internal
+    helper inside an extern "C" block would be exported under a C name any caller's symbol could collide with)."""
+    nm = subprocess.run(["nm", "-D", "--defined-only", rtlib_path], capture_output=True, text=True, check=True).stdout
+    defined = {m.group(1) for m in re.finditer(r"^[0-9a-f]+ T (\S+)$", nm, re.M)}
+    c_names = {n for n in defined if not n.startswith("_Z")} - TOOLCHAIN_SYMBOLS
+    assert c_names, "nm listed no unmangled text symbol: the pattern above no longer matches its output"
+    assert sorted(c_names - set(_declared_functions())) == []
+
+
 def test_library_is_built_from_this_tree(rtlib_path):
     """The build stamp (rtamd/provenance.py) matches the library and the sources in the tree."""
     from rtamd import provenance

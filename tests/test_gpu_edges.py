@@ -131,7 +131,7 @@ def test_tiny_frames_on_overlapped_lanes(gpu_lib, w, h):
 def test_null_stream_device_outputs_ordered(gpu_lib, lanes):
     """rt_render with device outputs and no stream (opts.stream NULL) runs on a non-blocking stream of the scene; it
     is ordered after the caller's null-stream work enqueued before the call and, without "overlap", before the null
-    stream's work after it (rt_api.cpp order_null), as a drop-in caller of the reference's render-into-my-surface
+    stream's work after it (render.cpp order_null), as a drop-in caller of the reference's render-into-my-surface
     loop (Renderer.cu:305-317) expects.  Each iteration queues a long fill on torch's default (null) stream, a fill
     of the output with junk, the frame with RT_RENDER_NO_SYNC and no stream, and a copy of the output — no host
     synchronisation anywhere — and every copy equals the synchronously rendered frame byte for byte.  With

@@ -290,7 +290,7 @@ def _sched_class(c):
     return 15 - np.clip(k, 0, 15)
 
 
-# the claim-order settings the library fixes (rt_api.cpp; options until round 5): 8 XCD bands, heavy units in quarters
+# the claim-order settings the library fixes (scene.hpp; options until round 5): 8 XCD bands, heavy units in quarters
 # from class level 12 (no halves), two adjacent units below level 6 merged into one item, costs recorded on one launch
 # in 8 and the order rebuilt on the next
 PARTS, K_HALF, K_QUARTER, K_MERGE, PERIOD, SCHED_THREADS = 8, 12, 12, 6, 8, 256
