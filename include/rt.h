@@ -260,7 +260,17 @@ rt_status rt_scene_update(rt_scene *scene, uint64_t frame);
 /* Device half of one iteration of startRender (src/Global/Renderer.cu:305-317) = the
  * `render` kernel (src/Global/Kernel.cu:105-147).  Unless RT_RENDER_SKIP_UPDATE is set,
  * first calls rt_scene_update(scene, frame).  Host outputs (may be NULL) receive the
- * frame after completion; device outputs are described in rt_render_opts. */
+ * frame after completion; device outputs are described in rt_render_opts.
+ *
+ * Traversal depth: a ray's traversal stack holds 64 entries, the reference's (BLAS.cu:129, TLAS.cu:138): 16 in
+ * LDS, the rest paged to scratch in half-windows of 8.  A traversal that needs more loses 8 of its entries (the
+ * half-window paged out last is overwritten) and goes on, so the pixel may miss geometry.  This is reported
+ * only with RT_RENDER_COUNT_WORK and without RT_RENDER_NO_SYNC: the call then returns RT_ERR_UNSUPPORTED
+ * ("traversal stack overflow") after the frame and its outputs are complete.  Without COUNT_WORK, and for
+ * frames collected later (rt_scene_collect), an overflow is silent.  A binary tree holds one entry per level of
+ * the current path and a TLAS leaf's remainder; a quad tree ("wide") at most 3 per two binary levels and 2 more
+ * at a leaf: with tlas_height + blas_height_max <= 40 (rt_scene_info) no kernel reaches the 64 entries.  Deep
+ * chains that page without overflowing are pinned by tests/test_gpu_deep_stack.py. */
 rt_status rt_render(rt_scene *scene, uint64_t frame, const rt_render_opts *opts,
                     uint8_t *rgba8_host, float *rgb32_host, rt_stats *stats);
 
@@ -305,7 +315,9 @@ rt_status rt_tile_pixels(uint32_t width, uint32_t height, uint32_t tile_w, uint3
 
 /* Trace arbitrary world rays (origin xyz, direction xyz per ray) against the current TLAS
  * with t in [0.001, inf) and return the closest hit (TLAS::hit, src/AS/TLAS.cu:131-201).
- * RT_ERR_STATE after rt_scene_update_triangles until a frame has run its update. */
+ * RT_ERR_STATE after rt_scene_update_triangles until a frame has run its update.
+ * A traversal deeper than the 64 stack entries (see rt_render) is not reported here: the kernel counts the
+ * overflow per lane and discards the count, and the ray's record is whatever the remaining entries give. */
 rt_status rt_trace_rays(rt_scene *scene, const float *rays_host, size_t ray_count,
                         uint32_t flags, rt_hit *hits_host);
 
@@ -352,7 +364,9 @@ rt_status rt_trace_rays(rt_scene *scene, const float *rays_host, size_t ray_coun
  *            scene's device — all before anything is enqueued; RT_ERR_STATE before rt_scene_build and after
  *            rt_scene_update_triangles until a frame has run its update.  ray_count == 0 returns RT_OK and launches
  *            nothing.  The caller's current device is preserved.  Allowed while a communicator is attached: the query
- *            is local to this rank and launches no RCCL work. */
+ *            is local to this rank and launches no RCCL work.  A traversal deeper than the 64 stack entries (see
+ *            rt_render) is not an error here either: the query kernel has no counter output, the overflow count
+ *            stays in the lane, and the ray's answer comes from the entries that were kept. */
 typedef enum rt_query_flags {
     RT_QUERY_EXACT   = 1u << 0,  /* the EXACT build's arithmetic and visit order (as RT_RENDER_EXACT) */
     RT_QUERY_ANY_HIT = 1u << 1,  /* occlusion: stop at the first accepted hit */

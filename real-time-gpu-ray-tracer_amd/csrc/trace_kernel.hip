@@ -430,9 +430,11 @@ struct LaneCount { uint32_t pairs, tri, sq, quad, inst, hits, overflow; };
 // Per-lane traversal stack: a window of LDS_DEPTH entries in LDS (layout [depth][BLOCK]: a wave's
 // 64 lanes touch 64 consecutive u64 at any depth -> bank-conflict-free ds_*_b64) backed by a
 // scratch array.  Push/pop only touch LDS; when the window fills, its bottom half is paged out to
-// scratch, and when it empties the most recent half-page is paged back in (rare: median-split
-// trees stay within 16 entries up to ~1k instances x 1k triangles).  Capacity LDS_DEPTH +
-// SPILL_DEPTH = 64 entries, the reference's stack size (BLAS.cu:129, TLAS.cu:138).
+// scratch, and when it empties the most recent half-page is paged back in.  Median-split trees stay
+// within 16 entries up to ~1k instances x 1k triangles, but GPU-built (LBVH) trees over clustered
+// centroids are chains and page on nearly every ray: tests/test_gpu_deep_stack.py pins every paging
+// site on trees 29 and 10 + 29 levels deep.  Capacity LDS_DEPTH + SPILL_DEPTH = 64 entries, the
+// reference's stack size (BLAS.cu:129, TLAS.cu:138).
 struct SEnt { uint32_t ref; uint32_t tn; };   // node ref, entry t (float bits)
 // LDS entries are stored packed as u64 (low = ref, high = entry t bits)
 typedef __attribute__((address_space(3))) unsigned long long LdsU2;
@@ -470,7 +472,7 @@ __device__ __forceinline__ void spill_load(const SEnt *src, Stack &stk) {
 __device__ __forceinline__ void stack_page_out(Stack &stk, SEnt *spill, LaneCount &c) {
     if (stk.spilled + HALF > SPILL_DEPTH) {        // deeper than the reference's 64 entries
         c.overflow++;
-        stk.spilled = SPILL_DEPTH - HALF;          // drop the oldest half-page (result flagged)
+        stk.spilled = SPILL_DEPTH - HALF;          // the last half-page in scratch is overwritten (result flagged)
     }
     spill_store(spill + stk.spilled, stk);
 #pragma unroll
