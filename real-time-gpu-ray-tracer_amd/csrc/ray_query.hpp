@@ -12,7 +12,7 @@
 // count, the traversal by the trees.
 //
 // A ray's range is [TMIN, tmax[i]] with the reference's in_range semantics: the traversal starts with T.tmax =
-// tmax[i] instead of +inf (trav_init's tmax overload), so every box and primitive test sees the caller's bound exactly
+// tmax[i] instead of +inf (trav_init's tmax argument), so every box and primitive test sees the caller's bound exactly
 // as it sees the closest hit so far.  !(tmax > TMIN), NaN included, is a miss without traversal.
 //
 // ANY (occlusion): a lane stops after the first round in which it accepted a hit.  The any-hit traversal is a prefix
@@ -47,8 +47,8 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
     T.tracing = false;
     T.found = false;
     alignas(16) SEnt spill[SPILL_DEPTH];
-    LaneCount cnt = {0, 0, 0, 0, 0, 0, 0};
-    PhaseCycles pc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    LaneCount cnt = {};
+    PhaseCycles pc = {};
     uint32_t steps = 0;
 
     bool has = false;                  // lane owns a ray
@@ -120,7 +120,7 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
                 q.occluded[idx] = T.found ? 1 : 0;
             } else {
                 if (q.t) q.t[idx] = T.found ? T.hit.t : __builtin_huge_valf();
-                if (q.hits) {                     // the record rt_trace_rays writes (trace_rays_kernel)
+                if (q.hits) {                     // the record rt_trace_rays writes (trace_rays_kernel: keep the two alike)
                     rt_hit r;
                     if (T.found) {
                         const Hit h = T.hit;

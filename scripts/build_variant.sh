@@ -2,6 +2,7 @@
 # Build an A/B variant of librtamd.so whose FAST trace kernel gets extra defines:
 #   scripts/build_variant.sh NAME "-DFOO=1 -DBAR=2"   ->  real-time-gpu-ray-tracer_amd/lib/librtamd_NAME.so
 #   SRC=path/to/trace_kernel.hip (optional): another version of the kernel source (e.g. git show HEAD:...)
+#     (SRC swaps only the .hip file: the device headers it includes, vecmath.hpp ... shade.hpp, come from the working tree)
 # (load it with RTAMD_LIB=...; everything else is the default build's objects)
 set -e
 cd "$(dirname "$0")/../real-time-gpu-ray-tracer_amd/csrc"

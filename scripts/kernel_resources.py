@@ -1,21 +1,48 @@
 #!/usr/bin/env python3
 """VGPR / spill / scratch of every non-counting instantiation of the persistent kernel in built trace objects
 (register budget check after a traversal edit; WIDE 0 binary pairs, 1 quads by entry t, 2 quads in pair order; RAW 1 =
-GPU-built scenes without cold records).  usage: scripts/kernel_resources.py real-time-gpu-ray-tracer_amd/build/trace_*.o"""
+GPU-built scenes without cold records).  usage: scripts/kernel_resources.py real-time-gpu-ray-tracer_amd/build/trace_*.o
+
+--hash: instead, for every object given (any object that holds kernels), the sha256 (first 16 hex digits) of its gfx950
+code object's .text bytes, .rodata bytes and `llvm-readelf --notes` output (kernel descriptors: registers, LDS, scratch,
+arguments).  A refactor that must not change the device code compares these between a build of the parent commit and
+one of the branch (profiles/refactor_*/README.md).  usage: scripts/kernel_resources.py --hash build/*.o"""
+import hashlib
 import re
 import subprocess
 import sys
 import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-for obj in sys.argv[1:]:
+
+
+def code_object(obj, d):
+    """Unbundle the gfx950 code object of a host object into directory d; returns its path."""
+    fb, co = f"{d}/fb", f"{d}/co"
+    subprocess.run(["objcopy", "--dump-section", f".hip_fatbin={fb}", obj], check=True)
+    subprocess.run([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    f"--input={fb}", f"--output={co}", "--unbundle"], check=True)
+    return co
+
+
+def notes_of(co):
+    return subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
+
+
+def print_hashes(obj):
+    h = lambda b: hashlib.sha256(b).hexdigest()[:16]
     with tempfile.TemporaryDirectory() as d:
-        fb = f"{d}/fb"
-        subprocess.run(["objcopy", "--dump-section", f".hip_fatbin={fb}", obj], check=True)
-        co = f"{d}/co"
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                        f"--input={fb}", f"--output={co}", "--unbundle"], check=True)
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
+        co = code_object(obj, d)
+        for sec in (".text", ".rodata"):
+            subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", f"--only-section={sec}", co, f"{d}/sec"], check=True)
+            with open(f"{d}/sec", "rb") as f:
+                print(f"{obj.split('/')[-1]} {sec} {h(f.read())}")
+        print(f"{obj.split('/')[-1]} notes {h(notes_of(co).encode())}")
+
+
+def print_resources(obj):
+    with tempfile.TemporaryDirectory() as d:
+        notes = notes_of(code_object(obj, d))
     for e in notes.split("- .agpr_count")[1:]:
         name = re.search(r"\.name:\s+(\S+)", e).group(1)
         m = re.search(r"render_persistent_kernelILb([01])ELi(\d)ELi(\d)ELi(\d)E", name)
@@ -25,3 +52,10 @@ for obj in sys.argv[1:]:
         g = lambda k: re.search(rf"\.{k}:\s+(\d+)", e).group(1)
         print(f"{obj.split('/')[-1]:22s} {label:22s} vgpr {g('vgpr_count'):>3} vspill {g('vgpr_spill_count'):>3} "
               f"sgpr {g('sgpr_count'):>3} sspill {g('sgpr_spill_count'):>3} scratch {g('private_segment_fixed_size')}")
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    hashes = "--hash" in args
+    for obj in (a for a in args if a != "--hash"):
+        (print_hashes if hashes else print_resources)(obj)

@@ -13,7 +13,8 @@ For C2 (1080p, 1 spp, depth 2; also at depth 1) and C3 (1080p, 4 spp, depth 4), 
   * "<mode>+opt=v+...": any of the above with extra set_option calls (e.g. "fast_compat+lds_scene=0+kernel=0")
 and compares each with the oracle's frame: pixels with any RGBA8 channel |d| > 1 (outliers), max |d|, and the
 per-channel float |d| of the linear RGB.  Output: one JSON object (stdout, or --out).
-RTAMD_LIB selects the library (variant builds, e.g. RT_SLAB_CONS=0).
+RTAMD_LIB selects the library (variant builds; the conservative slabs and exact re-takes of DESIGN §3.3 are no longer
+build options).
 """
 from __future__ import annotations
 

@@ -1,7 +1,7 @@
 """Deep-tree scenes and a CPU model of the trace kernels' traversal stack — TEST INFRASTRUCTURE ONLY.
 
 Every trace kernel keeps a per-lane stack window of 16 entries in LDS and pages half-windows of 8 entries out to and
-back from scratch (csrc/trace_kernel.hip, struct Stack).  Balanced trees never fill the window, so the paging code runs
+back from scratch (csrc/stack.hpp, struct Stack).  Balanced trees never fill the window, so the paging code runs
 only on deep trees.  This module makes such trees on purpose and says, per ray, how deep the stack gets:
 
 * `deep_blas()` / `deep_two_level()`: two fixed scenes whose GPU-built (RT_BUILD_LBVH) trees are chains.  The triangle
@@ -31,7 +31,7 @@ from lbvh_ref import lbvh_tree
 from rtamd import abi, scenes
 
 F32 = np.float32
-LDS_DEPTH, HALF = 16, 8            # csrc/trace_kernel.hip: the window and the half-page
+LDS_DEPTH, HALF = 16, 8            # csrc/trace_kernel.hip, csrc/stack.hpp: the window and the half-page
 TMIN = F32(0.001)
 CODE_BITS = 30
 PER_CLUSTER = 3

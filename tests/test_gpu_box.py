@@ -135,7 +135,7 @@ def on_parallel_face(b, r):
 @pytest.mark.parametrize("mode", CULL_MODES)
 def test_cull_modes_never_miss_a_reference_hit(gpu_lib, cases, mode):
     """The greedy-quad (host SAH) instances cull conservatively: a superset of the reference's hits, but for the one
-    documented exception (trace_kernel.hip RT_SLAB_CONS / XD_PAR): a ray with a parallel axis whose origin lies exactly
+    documented exception (csrc/box.hpp, the conservative slabs / XD_CULL; not a build option): a ray with a parallel axis whose origin lies exactly
     on a face of that axis's slab, which the reference keeps (BoundingBox.cu:47) and reciprocal planes cannot represent.
     The crafted cases hold ~400 such rays; every reference hit outside that case is kept."""
     b, r, tm, hit, te, n0 = cases                              # the first n0 cases: tmax = +inf

@@ -1,7 +1,7 @@
 """Traversal-stack paging and the GPU builder on chains and ties, on the two deep scenes of tests/deep_tree_ref.py.
 
-Every trace kernel keeps 16 stack entries per lane in LDS and pages half-windows to scratch (csrc/trace_kernel.hip,
-struct Stack: stack_page_out, stack_page_out3, stack_page_in).  On these scenes the GPU-built trees are chains 29 (BLAS)
+Every trace kernel keeps 16 stack entries per lane in LDS and pages half-windows to scratch (csrc/stack.hpp,
+struct Stack: stack_page_out from stack_push and from the quad step's three-entry push, stack_page_in).  On these scenes the GPU-built trees are chains 29 (BLAS)
 and 10 + 29 (TLAS + BLAS) levels deep with equal Morton codes in them; tests/test_deep_tree_ref.py shows with a CPU model
 that 99 % of the rays page out once, 72 % / 99 % twice or more, 46 % take their closest hit from an entry that came back
 through a page-in, and that no kernel form can reach the 64-entry capacity (nothing here may report an overflow).

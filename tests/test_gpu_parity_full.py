@@ -116,9 +116,9 @@ def test_fast_kernel_on_reference_trees(gpu_lib, case, wide):
     """Identical trees (the reference's median split), FAST kernel (persistent waves, reciprocal-slab culls, LDS
     scene) with the reference's visit order on binary node pairs ("wide" 0) and on the default quads (two binary
     levels per quad, visited in the same pair order).  The kernel's arithmetic is the reference's wherever a value
-    reaches a hit or a pixel; its box culls are conservative (RT_SLAB_CONS), and on these trees every box decision —
+    reaches a hit or a pixel; its box culls are conservative (csrc/box.hpp), and on these trees every box decision —
     and every pair-order comparison — that lies inside the reciprocal slab's error margin is re-taken with the
-    reference's division slab (RT_BOX_EXACT, XBOX instances), so the traversal takes the reference's decisions: the
+    reference's division slab (the exact re-takes of the XBOX instances; neither is a build option), so the traversal takes the reference's decisions: the
     float frame is bit-identical (round 4, without the re-test: 1 pixel on 5 of 20 renders, a hit on a box boundary
     the reference's own slab rounding culls; profiles/r04/c5_compat_residual/, profiles/r05/exact_box/)."""
     name, scene, W, H, cam, orc = case
