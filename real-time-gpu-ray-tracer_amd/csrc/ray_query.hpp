@@ -110,8 +110,7 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
                 T.tracing = false;
                 T.cur = REF_NONE;
                 T.pleaf = REF_NONE;
-                T.stk.sp = 0;
-                T.stk.spilled = 0;
+                T.stk.clear();
             }
         }
         // ---- retire the lanes whose ray finished

@@ -14,8 +14,7 @@ struct Hit {
 
 // Resumable per-lane traversal state: TLAS::hit (TLAS.cu:131-201) as a state machine so that a
 // persistent wave can interleave traversal steps with shading / ray regeneration of other lanes.
-constexpr uint32_t REF_NONE = 0xFFFFFFFFu;   // leaf bit + primitive type 3: never a real ref
-
+// (REF_NONE: stack.hpp)
 struct Trav {
     RayP wr, lr;           // world-space ray, instance-space ray of cur_inst
     float tmax;            // currentRange.max
@@ -51,8 +50,7 @@ __device__ __forceinline__ void trav_init(Trav &T, const TreeRoot &R, const f3 &
     T.lr = T.wr;
     T.tmax = tmax;
     T.found = false;
-    T.stk.sp = 0;
-    T.stk.spilled = 0;
+    T.stk.clear();
     T.cur = R.ref;
     T.cur_inst = 0;
     T.pleaf = REF_NONE;

@@ -9,7 +9,7 @@ cd "$(dirname "$0")/../real-time-gpu-ray-tracer_amd/csrc"
 make -s
 NAME=$1; FLAGS=$2
 HIPCC=/opt/rocm/bin/hipcc
-$HIPCC -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -mllvm -amdgpu-use-amdgpu-trackers -DRT_EXACT=0 -DRT_FAST_IEEE=1 -ffp-contract=off $FLAGS \
+$HIPCC -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -mllvm -amdgpu-use-amdgpu-trackers -fno-slp-vectorize -DRT_EXACT=0 -DRT_FAST_IEEE=1 -ffp-contract=off $FLAGS \
   -I. -I$PWD -c ${SRC:-trace_kernel.hip} -o ../build/trace_fast_$NAME.o
 # the default library's objects (the Makefile knows them) without the one replaced here
 objs=$(make -s link-objs | tr ' ' '\n' | grep -v '/trace_fast\.o$' | tr '\n' ' ')
