@@ -43,6 +43,18 @@ Tree tree_from_pairs(const TreeRoot &root, const std::vector<NodePair> &pairs, u
     return t;
 }
 
+// Node pairs the last GPU BLAS build wrote.  rt_scene::blas_pair_count is read back once, at rt_scene_build; a rebuild
+// after rt_scene_update_triangles keeps another number of interior nodes, and a reader that copied the older count
+// would miss pairs the roots refer to.  Host-built BLASes (a GPU TLAS over SAH trees) keep their one count.
+rt_status gpu_blas_pairs(const rt_scene *s, size_t &count) {
+    count = s->blas_pair_count;
+    if (s->build_mode != RT_BUILD_LBVH || !s->blas_builder) return RT_OK;
+    uint32_t n = 0;
+    HIP_TRY(hipMemcpy(&n, s->gpu_counts.p, sizeof n, hipMemcpyDeviceToHost));
+    count = std::min<size_t>(n, s->blas_pairs.n);
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -138,8 +150,10 @@ rt_status rt_scene_debug_read(rt_scene *s, const char *name, void *dst, size_t c
         RT_TRY(drain(s));
         const void *from = k == "blas_pairs" ? (const void *)s->blas_pairs.p
                                              : (k == "blas_quads" ? (const void *)s->blas_quads.p : (const void *)s->blas_roots.p);
+        size_t pair_count = 0;
+        RT_TRY(gpu_blas_pairs(s, pair_count));
         *bytes = k == "blas_roots" ? s->blas_roots.n * sizeof(TreeRoot)
-                                   : s->blas_pair_count * (k == "blas_pairs" ? sizeof(NodePair) : sizeof(NodeQuad));
+                                   : pair_count * (k == "blas_pairs" ? sizeof(NodePair) : sizeof(NodeQuad));
         if (capacity && *bytes) HIP_TRY(hipMemcpy(dst, from, std::min(capacity, *bytes), hipMemcpyDeviceToHost));
         return RT_OK;
     } else if (k == "leaf_prims") {
@@ -186,7 +200,9 @@ rt_status rt_scene_export_blas(const rt_scene *s, uint32_t b, float *boxes, uint
         std::vector<TreeRoot> roots;
         if (s->seg_of_blas[b] == 0xFFFFFFFFu)
             return fail(RT_ERR_STATE, "this BLAS is not built: its instance group is one BLAS (option \"group\")");
-        HIP_TRY(read_back(pairs, s->blas_pairs.p, s->blas_pair_count));
+        size_t pair_count = 0;
+        RT_TRY(gpu_blas_pairs(s, pair_count));
+        HIP_TRY(read_back(pairs, s->blas_pairs.p, pair_count));
         HIP_TRY(read_back(roots, s->blas_roots.p, s->blas_roots.n));
         const uint32_t type = s->blas[b].type;
         std::vector<uint32_t> orig;

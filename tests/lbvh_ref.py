@@ -34,8 +34,18 @@ def _expand10(v: np.ndarray) -> np.ndarray:
     return v.astype(np.uint32)
 
 
-def morton_codes(cents: np.ndarray) -> np.ndarray:
+INACTIVE_CODE = 0xFFFFFFFF
+
+
+def morton_codes(cents: np.ndarray, active=None) -> np.ndarray:
+    """active (bool per item, None = all): an inactive item (a TLAS record kept out of the tree, morton_kernel's
+    centroid w != 0) is left out of the centroid bounds and gets the code 0xFFFFFFFF, behind every 30-bit code."""
     c = np.asarray(cents, F32)
+    live = np.ones(c.shape[0], bool) if active is None else np.asarray(active, bool)
+    codes = np.full(c.shape[0], INACTIVE_CODE, np.uint32)
+    if not live.any():
+        return codes
+    c = c[live]
     lo, hi = c.min(axis=0), c.max(axis=0)
     q = np.zeros(c.shape, np.uint32)
     for a in range(3):
@@ -45,15 +55,17 @@ def morton_codes(cents: np.ndarray) -> np.ndarray:
         x = ((c[:, a] - lo[a]) / ext * F32(1024.0)).astype(F32)
         qa = np.where(x > 0, np.minimum(np.floor(x), 1023), 0)
         q[:, a] = np.where(x >= 1023, 1023, qa).astype(np.uint32)
-    return (_expand10(q[:, 0]) << 2) | (_expand10(q[:, 1]) << 1) | _expand10(q[:, 2])
+    codes[live] = (_expand10(q[:, 0]) << 2) | (_expand10(q[:, 1]) << 1) | _expand10(q[:, 2])
+    return codes
 
 
-def lbvh_tree(boxes: np.ndarray, cents: np.ndarray, cap: int):
+def lbvh_tree(boxes: np.ndarray, cents: np.ndarray, cap: int, active=None):
     """-> (node_boxes[n,6] f32, node_count_index[n,2] u32, refs[items] u32) in reference form;
-    refs are item indices (0-based positions in `boxes`)."""
+    refs are item indices (0-based positions in `boxes`).  active: see morton_codes; an inactive item's box is
+    taken as given (the builder's callers make it all +inf, launch_instance_update's inf_inactive)."""
     boxes = np.asarray(boxes, F32).reshape(-1, 6)
     n = boxes.shape[0]
-    codes = morton_codes(cents)
+    codes = morton_codes(cents, active)
     order = np.argsort(codes, kind="stable")
     keys = [int(k) for k in codes[order]]
 
@@ -125,3 +137,12 @@ def check_tree(node_boxes, ci, refs, item_boxes, cap):
         assert np.array_equal(node_boxes[j], union(node_boxes[idx:idx + 2])), j
         todo += [(idx, d + 1), (idx + 1, d + 1)]
     return height
+
+
+def assert_tree_equal(got, want, what=None):
+    """Two trees in reference form are the same bytes: topology (count / index), leaf order, node boxes."""
+    nb, ci, refs = got
+    wb, wci, wrefs = want
+    assert np.array_equal(ci, wci), what
+    assert np.array_equal(refs, wrefs), what
+    assert np.array_equal(nb, wb), what

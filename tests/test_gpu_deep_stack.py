@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 import deep_tree_ref as D
-from lbvh_ref import check_tree, lbvh_tree
+from lbvh_ref import assert_tree_equal, check_tree, lbvh_tree
 from rtamd import Renderer, abi
 from test_gpu_lbvh import PAIR_DT, QUAD_DT, ROOT_DT, _expected_quads, frac_within
 from test_gpu_ray_query import closest, occluded
@@ -52,14 +52,6 @@ def build(case, mode, opts):
     for k, v in opts.items():
         r.set_option(k, v)
     return r.build_acceleration_structure(0, mode=mode)
-
-
-def assert_tree_equal(got, want, what):
-    nb, ci, refs = got
-    wb, wci, wrefs = want
-    assert np.array_equal(ci, wci), what
-    assert np.array_equal(refs, wrefs), what
-    assert np.array_equal(nb, wb), what
 
 
 # ---- a. the builder on chains and ties ---------------------------------------------------------------------------------

@@ -7,6 +7,11 @@
   against the oracle (compat trees), as RT_BUILD_SAH is (DESIGN.md §3.4);
 * rebuilding every frame is deterministic (same bytes), and rt_scene_update_triangles followed by
   the GPU rebuild gives the same frame as a scene created with the moved triangles.
+
+The scenes here build trees of few sizes (1, 93, 1024, 3000, 5000, 65 536, 81 920 items).  tests/test_gpu_lbvh_sizes.py
+pins the builder at the item counts where it switches code paths (one-leaf trees, sort padding, 2048 / 2049, chunk
+edges, the quad frontier's LDS limit, TLASes around 512 and 2048 records, inactive TLAS records), on tied codes and a
+flat axis, and rt_scene_update_triangles over a range with first > 0.
 """
 import ctypes as C
 
