@@ -134,7 +134,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
                                        s->inst_blas.p, s->blas_roots.p, s->blas_wide_refs.p, /*inf_inactive=*/!small, cs));
         s->chain_stream[b] = cs;
         if (small) {
-            // one workgroup: the LBVH TLAS over the live records, quads, slots, slot-ordered records (lbvh.hip)
+            // one workgroup: the LBVH TLAS over the live records, quads, slots, slot-ordered records (lbvh_tlas_small.hpp)
             SmallTlasArgs a{};
             a.n = n;
             a.hot = reinterpret_cast<const InstHot *>(fd + s->off_hot); a.cold = reinterpret_cast<const InstCold *>(fd + s->off_cold);

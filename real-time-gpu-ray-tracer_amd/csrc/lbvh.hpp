@@ -1,4 +1,4 @@
-// lbvh.hpp — host interface of the GPU BVH builder (RT_BUILD_LBVH, lbvh.hip).
+// lbvh.hpp — host interface of the GPU BVH builder (RT_BUILD_LBVH; lbvh.hip, which maps its device headers lbvh_*.hpp).
 //
 // The reference builds every BLAS once and the TLAS every frame on the host with a random-axis
 // median split (src/AS/BLAS.cu:4-117, src/AS/TLAS.cu:4-129, driven from Renderer.cu:123-155 and
@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "devbuf.hpp"
 #include "layout.hpp"
 #include "../../include/rt.h"
 
@@ -129,46 +130,56 @@ public:
     // (after the stream has passed them).  Each record between two kernels idles the GPU ~5 us.
     static constexpr int STAGES = 9;
     static const char *const STAGE_NAMES[STAGES];
+    // the event mark(k) records: EV_START opens stage 0, the event named after a stage closes it
+    enum StageEvent { EV_START, EV_PREP, EV_BOUNDS, EV_MORTON, EV_SORT, EV_HIERARCHY_SMALL, EV_HIERARCHY_LARGE, EV_SCAN,
+                      EV_EMIT_ROOTS, EV_COLLAPSE };
+    static_assert(EV_COLLAPSE == STAGES, "one event per stage after EV_START");
     hipError_t set_timing(bool on);
     hipError_t stage_ms(float (&ms)[STAGES]) const;
 
 private:
     uint32_t n_items_ = 0, n_segs_ = 0, max_count_ = 0;
     std::vector<std::pair<uint32_t, uint32_t>> big_segs_;   // {item_base, count} of trees sorted by rocPRIM
-    LbvhSeg *segs_ = nullptr;
-    uint32_t *seg_of_ = nullptr;          // item -> segment
-    uint32_t *members_ = nullptr;         // group segments: {first primitive, instance} pairs
-    size_t members_n_ = 0;
-    uint32_t *item_member_ = nullptr;     // per item: its member instance + 1 (group segments), from members_
-    float *box_ = nullptr;                // 6 floats per item (owned or caller's)
+    // The device workspace.  Every DevBuf below is also named in each_buf(), which release() and workspace_bytes() walk;
+    // one handed to a kernel is allocated (DevBuf::alloc: never null) even where it holds no element.
+    DevBuf<LbvhSeg> segs_;
+    DevBuf<uint32_t> seg_of_;             // item -> segment
+    DevBuf<uint32_t> members_;            // group segments: {first primitive, instance} pairs
+    DevBuf<uint32_t> item_member_;        // per item: its member instance + 1 (group segments), from members_
+    float *box_ = nullptr;                // 6 floats per item (own_box_ or the caller's)
     float4 *cent_ = nullptr;
-    float *own_box_ = nullptr;
-    float4 *own_cent_ = nullptr;
-    TriHot *stage_ = nullptr;             // prep_blas_items(stage_hot): TriHot per item, item order
+    DevBuf<float> own_box_;               // (lazy: prep_blas_items)
+    DevBuf<float4> own_cent_;
+    DevBuf<TriHot> stage_;                // prep_blas_items(stage_hot): TriHot per item, item order (lazy)
     bool stage_ready_ = false;
-    uint32_t *bounds_ = nullptr;          // 6 ordered-uint per segment (centroid bounds)
-    uint32_t *k0_ = nullptr, *k1_ = nullptr;           // Morton codes (per item, then sorted within each segment)
-    uint32_t *v0_ = nullptr, *v1_ = nullptr;
-    uint32_t *child_ = nullptr;           // 2 per interior node: LEAF_BIT | sorted position, or node
-    uint32_t *parent_ = nullptr;          // per interior node
-    uint32_t *parent_leaf_ = nullptr;     // per sorted position
-    uint32_t *range_ = nullptr;           // 2 per interior node: first, last sorted position
-    uint32_t *flag_ = nullptr;            // arrival counters
-    uint32_t *frontier_ = nullptr;        // trees > LOCAL_MAX items: [count, arrivals at chunk-crossing nodes]
-    uint32_t *height_ = nullptr;          // per interior node
-    float *nbox_ = nullptr;               // 6 per interior node
-    uint32_t *kept_ = nullptr, *pidx_ = nullptr;
-    uint32_t *front_ = nullptr;           // collapse_wide frontier of trees too large for LDS
-    uint32_t *count_ = nullptr;           // pairs written by the last build (when the caller passed no counter)
-    uint32_t *last_count_ = nullptr;      // the counter the last build wrote
+    DevBuf<uint32_t> bounds_;             // 6 ordered-uint per segment (centroid bounds)
+    DevBuf<uint32_t> k0_, k1_;            // Morton codes (per item, then sorted within each segment)
+    DevBuf<uint32_t> v0_, v1_;
+    DevBuf<uint32_t> child_;              // 2 per interior node: LEAF_BIT | sorted position, or node
+    DevBuf<uint32_t> parent_;             // per interior node
+    DevBuf<uint32_t> parent_leaf_;        // per sorted position
+    DevBuf<uint32_t> range_;              // 2 per interior node: first, last sorted position
+    DevBuf<uint32_t> flag_;               // arrival counters
+    DevBuf<uint32_t> frontier_;           // trees > LOCAL_MAX items: [count, arrivals at chunk-crossing nodes] (lazy: build)
+    DevBuf<uint32_t> height_;             // per interior node
+    DevBuf<float> nbox_;                  // 6 per interior node
+    DevBuf<uint32_t> kept_, pidx_;
+    DevBuf<uint32_t> front_;              // collapse_wide frontier of trees too large for LDS (lazy: collapse_wide)
+    DevBuf<uint32_t> count_;              // pairs written by the last build (when the caller passed no counter; lazy: build)
+    uint32_t *last_count_ = nullptr;      // the counter the last build wrote (count_ or the caller's)
+    DevBuf<uint8_t> tmp_;                 // rocPRIM's scratch: the larger of the sort's and the scan's
+    template <typename Self, typename F>
+    static void each_buf(Self &b, F f) {
+        f(b.segs_); f(b.seg_of_); f(b.members_); f(b.item_member_); f(b.own_box_); f(b.own_cent_); f(b.stage_); f(b.bounds_);
+        f(b.k0_); f(b.k1_); f(b.v0_); f(b.v1_); f(b.child_); f(b.parent_); f(b.parent_leaf_); f(b.range_); f(b.flag_);
+        f(b.frontier_); f(b.height_); f(b.nbox_); f(b.kept_); f(b.pidx_); f(b.front_); f(b.count_); f(b.tmp_);
+    }
     // a forest with a tree of more than this many items is collapsed one pair per thread (collapse_all_kernel)
     static constexpr uint32_t COLLAPSE_ALL_MIN = 65536;
-    void *tmp_ = nullptr;
-    size_t tmp_bytes_ = 0;
     hipEvent_t stage_ev_[STAGES + 1] = {};
     bool timing_ = false;
     bool last_timed_ = false;             // the last BLAS build recorded its stage events (stage_ms reads them)
-    hipError_t mark(int k, hipStream_t stream) { return timing_ ? hipEventRecord(stage_ev_[k], stream) : hipSuccess; }
+    hipError_t mark(StageEvent k, hipStream_t stream) { return timing_ ? hipEventRecord(stage_ev_[k], stream) : hipSuccess; }
 };
 
 }  // namespace rtamd

@@ -19,6 +19,7 @@
 #include "../../include/rt.h"
 #include "bvh_build.hpp"
 #include "comm.hpp"
+#include "devbuf.hpp"
 #include "error.hpp"
 #include "host_math.hpp"
 #include "layout.hpp"
@@ -81,21 +82,6 @@ struct InstGroup {
     InstState st;                  // the group as one instance: the shared transform, the union of the boxes
     std::vector<uint32_t> members;
     bool valid = true;
-};
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    // room for `want` elements: a buffer too small is freed and allocated anew (its contents are not kept)
-    hipError_t reserve(size_t want) {
-        if (n >= want) return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess) n = want;
-        return e;
-    }
 };
 
 // rt_scene_attach_comm: this scene is rank `rank` of a `world`-rank frame.  One communicator
@@ -392,7 +378,7 @@ struct rt_scene {
     hipEvent_t ev_render_done = nullptr;   // last trace launch finished (BLAS rebuilds wait on it)
     bool gpu_tlas_sah = false;          // option "gpu_tlas" (set before the build): RT_BUILD_SAH BLASes, per-frame TLAS on the GPU
     // option "tlas_small": GPU-built frames with at most SMALL_TLAS_MAX records in the TLAS build it in one workgroup
-    // (lbvh.hip tlas_small_kernel) instead of the ~17-launch chain
+    // (lbvh_tlas_small.hpp tlas_small_kernel) instead of the ~17-launch chain
     bool tlas_small = true;
     DevBuf<uint32_t> blas_wide_refs;    // host-built BLASes under a GPU TLAS: quad root ref per BLAS
     // instance records + TLAS built by kernels each frame: RT_BUILD_LBVH, or RT_BUILD_SAH with "gpu_tlas"

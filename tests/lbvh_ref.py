@@ -1,4 +1,4 @@
-"""numpy restatement of the GPU builder (real-time-gpu-ray-tracer_amd/csrc/lbvh.hip) — TEST
+"""numpy restatement of the GPU builder (real-time-gpu-ray-tracer_amd/csrc/lbvh.hip, lbvh_*.hpp) — TEST
 INFRASTRUCTURE ONLY, the checker of RT_BUILD_LBVH trees.
 
 The builder is this repository's own (the reference builds on the host only, src/AS/BLAS.cu:4-117),

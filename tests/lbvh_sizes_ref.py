@@ -1,4 +1,4 @@
-"""Scenes that put the GPU builder (csrc/lbvh.hip) on every one of its size thresholds and on degenerate centroid
+"""Scenes that put the GPU builder (csrc/lbvh.hip, lbvh_*.hpp) on every one of its size thresholds and on degenerate centroid
 sets — TEST INFRASTRUCTURE ONLY.  tests/test_lbvh_sizes_ref.py checks on the CPU that the inputs hit what they aim
 at; tests/test_gpu_lbvh_sizes.py compares the GPU's trees with tests/lbvh_ref.py on them.
 
@@ -33,8 +33,8 @@ KINDS = ("random", "planar", "same", "dup8")
 ORDERS = ("ascending", "shuffled")
 BLAS_LEAF = 4                      # LBVH_BLAS_LEAF_CAP
 TLAS_LEAF = 1                      # the library's fixed "tlas_leaf" for GPU-built TLASes (tests/deep_tree_ref.py)
-LOCAL_MAX = 2048                   # lbvh.hip: LOCAL_SORT_MAX = LOCAL_MAX
-CHUNK = 1024                       # lbvh.hip: LBVH_CHUNK
+LOCAL_MAX = 2048                   # lbvh_sort.hpp: LOCAL_SORT_MAX = LOCAL_MAX (a static_assert there)
+CHUNK = 1024                       # lbvh_hierarchy.hpp: LBVH_CHUNK
 HEIGHT_MAX = 20                    # a condition on the inputs (include/rt.h: tlas_height + blas_height_max <= 40)
 HALF_EXTENT = 1.0                  # triangle centroids in [-1, 1]^3 of their BLAS's frame
 HALF_EDGE = 0.02                   # vertices within +-0.02 of the centroid: an edge ~0.02 of the cloud's extent

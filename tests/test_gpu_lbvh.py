@@ -1,4 +1,4 @@
-"""RT_BUILD_LBVH: BLASes and the per-frame TLAS built on the GPU (lbvh.hip), through the C ABI.
+"""RT_BUILD_LBVH: BLASes and the per-frame TLAS built on the GPU (lbvh.hip, lbvh_*.hpp), through the C ABI.
 
 * every GPU-built BLAS equals the numpy restatement (tests/lbvh_ref.py) of the builder over the
   oracle's primitive boxes, bit for bit (node boxes, topology, leaf order);
@@ -420,7 +420,7 @@ def _expected_quads(pairs, root_ref):
 
 @pytest.mark.parametrize("mode", ["particles", "large", "group80"])
 def test_gpu_quad_collapse_equals_restatement(gpu_lib, mode):
-    """RT_BUILD_LBVH trees get the 4-wide form on the GPU (collapse_wide_kernel, lbvh.hip): every quad equals
+    """RT_BUILD_LBVH trees get the 4-wide form on the GPU (collapse_wide_kernel, lbvh_collapse.hpp): every quad equals
     the host collapse rule applied to the GPU's binary tree (bit for bit, slot order included), and the quad
     traversal — which visits the binary tree's order — renders the binary traversal's frame within the FAST
     tolerance, with the same ray count."""

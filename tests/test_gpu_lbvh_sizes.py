@@ -1,4 +1,4 @@
-"""The GPU builder (csrc/lbvh.hip) at its size thresholds and on degenerate centroid sets, on the scenes of
+"""The GPU builder (csrc/lbvh.hip, lbvh_*.hpp) at its size thresholds and on degenerate centroid sets, on the scenes of
 tests/lbvh_sizes_ref.py (tests/test_lbvh_sizes_ref.py checks on the CPU that they hit what they aim at).
 
 The builder picks its code path by item count, and nothing but tests/lbvh_ref.py says what a GPU-built tree should be:
