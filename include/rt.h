@@ -467,11 +467,14 @@ rt_status rt_box_test(int device, const float *boxes_host, const float *rays_hos
 rt_status rt_scene_set_option(rt_scene *scene, const char *key, int64_t value);
 
 /* Debug buffers of the last launch that recorded them (synchronises the scene's stream):
- *   "timeline": 16 u64 per wave of the persistent kernel: start and end s_memrealtime (100 MHz),
+ *   "timeline": 24 u64 per wave of the persistent kernel: start and end s_memrealtime (100 MHz),
  *               (HW_ID << 32) | XCC_ID, pixels finished by the wave, time the queue ran dry,
  *               traversal rounds, shade phases, queue grabs, and (diagnostic builds only) shader
  *               cycles spent refilling, descending, testing leaves and shading, descent-loop
- *               iterations, refill-loop iterations, 2 reserved;
+ *               iterations, refill-loop iterations, cycles claiming lanes and sampling scatter, lane
+ *               sums per descent iteration / TLAS leaf phase / BLAS leaf phase / shade step, lanes
+ *               postponing a leaf in the descent loop, descent iterations without a node step,
+ *               shaded hits and those on a path's last rough segment;
  *   "costmap" : 1 u32 per output pixel: traversal steps (interior steps + leaf phases) of its path;
  *   "unit_cost", "unit_order": option "reorder" — per 8x8 unit, the work the lane's last launch recorded
  *               (after the next launch's schedule: the costs that schedule read), and the claim order the

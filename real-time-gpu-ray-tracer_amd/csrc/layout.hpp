@@ -292,7 +292,7 @@ __host__ __device__ inline uint32_t split_log2(uint32_t cls, uint32_t k_half, ui
     const uint32_t k = (SCHED_CLASSES - 1) - cls;
     return k >= k_quarter ? 2u : (k >= k_half ? 1u : 0u);
 }
-constexpr uint32_t TIMELINE_WORDS = 20;
+constexpr uint32_t TIMELINE_WORDS = 24;
 
 // Counter slots (device uint64 array)
 enum CounterSlot : uint32_t {

@@ -88,6 +88,26 @@ __device__ __forceinline__ Surface finalize(const SceneGPU &sc, const f3 &wo, co
     return s;
 }
 
+// The closest hit's material word alone (Surface::material), from the records finalize takes it from: what a path's
+// last segment needs of a rough surface, whose point, normal and scattered direction nobody reads.
+template <bool LDSS = false, int RAW = 2>
+__device__ __forceinline__ uint32_t hit_material(const SceneGPU &sc, const Hit &h) {
+    if (h.ptype == RT_PRIM_TRIANGLE) {
+        if (RAW == 1 || (RAW == 2 && sc.raw_tris)) {
+            const rt_triangle &R = sc.raw_tris[__float_as_uint(sc.tri_hot[h.slot].pad0)];
+            return R.material_type == RT_MAT_ROUGH ? R.material_index : ((sc.rough_count + R.material_index) | MAT_METAL_BIT);
+        }
+        return sc.tri_cold[h.slot].material;
+    }
+#if !RT_EXACT
+    if (LDSS) {
+        if (h.ptype == RT_PRIM_SPHERE) return lds_or_global(sc.lds_sph_cold, sc.sph_cold, h.slot).material;
+        return lds_or_global(sc.lds_q_cold, sc.quad_cold, h.slot).material;
+    }
+#endif
+    return (h.ptype == RT_PRIM_SPHERE ? sc.sph_cold : sc.quad_cold)[h.slot].material;
+}
+
 template <bool COUNT>
 __device__ f3 ray_color(const SceneGPU &sc, const CameraGPU &cam, f3 o, f3 d, Rng &rng, Trav &T, SEnt *spill,
                         LaneCount &cnt, uint32_t &rays) {                      // Kernel.cu:6-103

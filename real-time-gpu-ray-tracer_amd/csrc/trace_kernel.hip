@@ -351,32 +351,43 @@ __device__ __forceinline__ void render_persistent_body(const SceneGPU &sc, const
             f3 no = T.wr.o, nd = T.wr.d;                                     // next segment
             if (T.found) {
                 if (COUNT) cnt.hits++;
-                const Surface s = finalize<WIDE != 0, RAW>(sc, T.wr.o, T.wr.d, T.hit);
-                DIAG_WAIT_VM();
-                DIAG_T(t_hit);
-                const uint32_t mi = s.material & ~MAT_METAL_BIT;
-                const float4 m = mat_lds ? lds_mat[mi] : reinterpret_cast<const float4 *>(sc.materials)[mi];
-                bool absorbed = false;
-                if (!(s.material & MAT_METAL_BIT)) {                         // Rough.cuh:14-29
-                    // the path's last segment (depth and samples exhausted): the scattered direction and
-                    // the pixel's RNG are never used again, so the draws are skipped (same image)
-                    if (depth + 1 < cam.depth || sample + 1 < S2) {
+                if (RT_DIAG) pc.hits++;
+                const uint32_t material = hit_material<WIDE != 0, RAW>(sc, T.hit);
+                const uint32_t mi = material & ~MAT_METAL_BIT;
+                if (depth + 1 >= cam.depth && !(material & MAT_METAL_BIT)) {
+                    // A path's last segment on a rough surface (Rough.cuh:14-29 never absorbs): only the albedo
+                    // reaches the pixel, so the surface is not reconstructed.  The scatter draws are consumed while
+                    // the pixel has samples left — they see the RNG stream they would have — and skipped after
+                    // the last one, whose stream nobody reads.
+                    if (RT_DIAG) pc.hits_last_rough++;
+                    const float4 m = mat_lds ? lds_mat[mi] : reinterpret_cast<const float4 *>(sc.materials)[mi];
+                    if (sample + 1 < S2) (void)random_space_vector(rng);
+                    thr = mul(thr, mk(m.x, m.y, m.z));
+                    depth++;
+                    path_done = true;
+                } else {
+                    const Surface s = finalize<WIDE != 0, RAW>(sc, T.wr.o, T.wr.d, T.hit);
+                    DIAG_WAIT_VM();
+                    DIAG_T(t_hit);
+                    const float4 m = mat_lds ? lds_mat[mi] : reinterpret_cast<const float4 *>(sc.materials)[mi];
+                    bool absorbed = false;
+                    if (!(s.material & MAT_METAL_BIT)) {                     // Rough.cuh:14-29
                         nd = add(s.n, random_space_vector(rng));
                         if (f_eq(dot(nd, nd), FZERO * FZERO)) nd = s.n;
+                    } else {                                                 // Metal.cuh:15-32
+                        nd = unit(sub(T.wr.d, scl(s.n, 2.0f * dot(T.wr.d, s.n))));
+                        if (m.w > 0.0f) nd = add(nd, scl(random_space_vector(rng), m.w));
+                        absorbed = !(dot(nd, s.n) > 0.0f);
                     }
-                } else {                                                     // Metal.cuh:15-32
-                    nd = unit(sub(T.wr.d, scl(s.n, 2.0f * dot(T.wr.d, s.n))));
-                    if (m.w > 0.0f) nd = add(nd, scl(random_space_vector(rng), m.w));
-                    absorbed = !(dot(nd, s.n) > 0.0f);
-                }
-                DIAG_ADD(pc.hit, t_hit);
-                if (absorbed) {
-                    path_done = true;                                        // throughput (Kernel.cu:85-87)
-                } else {
-                    thr = mul(thr, mk(m.x, m.y, m.z));
-                    no = s.p;
-                    depth++;
-                    path_done = depth >= cam.depth;                          // throughput on exhaustion
+                    DIAG_ADD(pc.hit, t_hit);
+                    if (absorbed) {
+                        path_done = true;                                    // throughput (Kernel.cu:85-87)
+                    } else {
+                        thr = mul(thr, mk(m.x, m.y, m.z));
+                        no = s.p;
+                        depth++;
+                        path_done = depth >= cam.depth;                      // throughput on exhaustion
+                    }
                 }
             } else {
                 thr = mul(thr, ld3(cam.background));
@@ -443,7 +454,15 @@ __device__ __forceinline__ void render_persistent_body(const SceneGPU &sc, const
             w[17] = pc.lanes_leaf_tlas;
             w[18] = pc.lanes_leaf_blas;
             w[19] = pc.lanes_shade;
+            w[20] = pc.lanes_postpone;
+            w[21] = pc.iters_idle;
         }
+    }
+    if (RT_DIAG && out.timeline) {     // per-lane counts: summed over the wave
+        const uint32_t wv = (uint32_t)((const unsigned long long *)T.stk.lds - &lds_stack[0][0]) >> 6;
+        unsigned long long *w = out.timeline + (unsigned long long)TIMELINE_WORDS * (blockIdx.x * (BLOCK / 64) + wv);
+        atomicAdd(&w[22], pc.hits);
+        atomicAdd(&w[23], pc.hits_last_rough);
     }
 }
 

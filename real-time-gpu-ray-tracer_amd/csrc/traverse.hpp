@@ -181,6 +181,10 @@ __device__ __forceinline__ void trav_step(Trav &T, const SceneGPU &sc, SEnt *spi
 //     N or any node on the way.
 // Hence leaves are processed in the reference order with the reference's tmax: same hits, same
 // primitive tests, same instance visits (only extra node-pair tests are speculative).
+// A leaf is postponed where it appears in cur — in the iteration whose node step produced it, and at the end of
+// the leaf phase when the re-tested successor is one — not in an iteration of its own: no leaf runs between the two
+// places, so tmax, every pop_keep decision and the lane's operations and their order are the same, and a lane
+// takes one interior iteration less per leaf.
 __device__ __forceinline__ void pop_next(Trav &T, const SEnt *spill) {
     while (!T.stk.empty()) {
         const SEnt e = stack_pop(T.stk, spill);
@@ -189,8 +193,14 @@ __device__ __forceinline__ void pop_next(Trav &T, const SEnt *spill) {
     }
     T.cur = REF_NONE;
 }
+// The leaf in cur (a real ref: REF_NONE carries the leaf bit too) waits in pleaf for the leaf phase; the lane goes on
+// with the next entry.  T.tracing stays set while pleaf is, whatever cur becomes.
+__device__ __forceinline__ void postpone_leaf(Trav &T, const SEnt *spill) {
+    T.pleaf = T.cur;
+    pop_next(T, spill);
+}
 
-// One interior-loop step of a lane whose cur is an interior node, or a leaf to postpone.
+// One interior-loop step of a lane whose cur is an interior node.
 #if !RT_EXACT
 // Quad node (option "wide", layout.hpp NodeQuad): 4 slab tests on SoA bounds; the hit slots are visited
 //   PAIR (quads of two binary levels: the reference's trees, GPU-built trees): in the reference's order — the two
@@ -357,32 +367,26 @@ __device__ __forceinline__ void spec_interior_step(Trav &T, const SceneGPU &sc, 
     const uint32_t cur = T.cur;
 #if !RT_EXACT
     if (WIDE) {
-        if (!(cur & REF_LEAF)) wide_interior_step<COUNT, (WIDE >= 2), XBOX(WIDE)>(T, sc, spill, cnt);
-        else { T.pleaf = cur; pop_next(T, spill); }        // postpone, keep walking
+        wide_interior_step<COUNT, (WIDE >= 2), XBOX(WIDE)>(T, sc, spill, cnt);
         return;
     }
 #endif
-    if (!(cur & REF_LEAF)) {
-        float e0 = 0.0f, e1 = 0.0f;
-        bool h0, h1;
-        const uint4 D = pair_test<COUNT, XBOX(WIDE)>(T, sc, cur, cnt, h0, h1, e0, e1);
-        if (h0 && h1) {
-            const bool right_near = e0 > e1;          // TLAS.cu:185-192 ordering
-            stack_push(T.stk, spill, right_near ? D.x : D.y, right_near ? e0 : e1, cnt);
-            T.cur = right_near ? D.y : D.x;
-            T.curT = right_near ? e1 : e0;
-            return;
-        }
-        if (h0 || h1) {
-            T.cur = h0 ? D.x : D.y;
-            T.curT = h0 ? e0 : e1;
-            return;
-        }
-        pop_next(T, spill);
-    } else {
-        T.pleaf = cur;                                // postpone, keep walking
-        pop_next(T, spill);
+    float e0 = 0.0f, e1 = 0.0f;
+    bool h0, h1;
+    const uint4 D = pair_test<COUNT, XBOX(WIDE)>(T, sc, cur, cnt, h0, h1, e0, e1);
+    if (h0 && h1) {
+        const bool right_near = e0 > e1;          // TLAS.cu:185-192 ordering
+        stack_push(T.stk, spill, right_near ? D.x : D.y, right_near ? e0 : e1, cnt);
+        T.cur = right_near ? D.y : D.x;
+        T.curT = right_near ? e1 : e0;
+        return;
     }
+    if (h0 || h1) {
+        T.cur = h0 ? D.x : D.y;
+        T.curT = h0 ? e0 : e1;
+        return;
+    }
+    pop_next(T, spill);
 }
 
 // Process the postponed leaf, then resume at cur (re-tested) — TLAS.cu:157-173 / BLAS.cu:153-176.
@@ -497,6 +501,10 @@ struct PhaseCycles {
     // lane occupancy (diagnostic builds): lanes stepping per interior iteration, lanes holding a TLAS / BLAS leaf per
     // leaf phase, lanes shaded per shade step (sums; the timeline divides by iters / rounds / shades)
     unsigned long long lanes_interior, lanes_leaf_tlas, lanes_leaf_blas, lanes_shade;
+    // lanes_postpone: leaves postponed in the interior loop (lane sums); iters_idle: interior iterations in which no
+    // lane took a node step;
+    // hits / hits_last_rough: shaded hits, and those on a path's last segment with a rough material (albedo only)
+    unsigned long long lanes_postpone, iters_idle, hits, hits_last_rough;
 };
 __device__ __forceinline__ unsigned long long stamp() {
     unsigned long long t;
@@ -514,7 +522,11 @@ __device__ __forceinline__ unsigned long long stamp() {
 #endif
 
 // One round: interior loop until every traversing lane holds a leaf, then the leaf phase.
-// steps (when `track`): the lane's interior steps + leaf phases, the pixel's cost for the work order
+// An iteration of the interior loop: a lane whose cur is an interior node takes its step; then a lane without a
+// postponed leaf whose cur is a leaf — the one the step just produced, or a segment's first node — postpones it and
+// goes on with the next entry.  Likewise after the leaf phase, when the successor that survived its re-test (or the
+// entered BLAS's root) is a leaf.
+// steps (when `track`): the lane's node steps + postponements + leaf phases, the pixel's cost for the work order
 // leaf_early (setting "leaf_early"): the interior loop also ends once no more than this many lanes are still looking
 // for a leaf while some hold one; the lanes without a leaf skip the leaf phase and go on descending next round
 template <bool COUNT, int WIDE = 0>
@@ -527,9 +539,19 @@ __device__ __forceinline__ void spec_round(Trav &T, const SceneGPU &sc, SEnt *sp
         if (!looking) break;
         if (leaf_early && (uint32_t)__popcll(looking) <= leaf_early && __any(T.tracing && T.pleaf != REF_NONE)) break;
         const bool active = T.tracing && T.cur != REF_NONE && (!(T.cur & REF_LEAF) || T.pleaf == REF_NONE);
-        if (RT_DIAG) pc.lanes_interior += (unsigned long long)__popcll(__ballot(active));
-        if (active) {
+        const bool node = active && !(T.cur & REF_LEAF);
+        if (RT_DIAG) {
+            pc.lanes_interior += (unsigned long long)__popcll(__ballot(active));
+            if (!__ballot(node)) pc.iters_idle++;
+        }
+        if (node) {
             spec_interior_step<COUNT, WIDE>(T, sc, spill, cnt);
+            if (track) steps++;
+        }
+        const bool leaf = active && T.pleaf == REF_NONE && (T.cur & REF_LEAF) && T.cur != REF_NONE;
+        if (RT_DIAG) pc.lanes_postpone += (unsigned long long)__popcll(__ballot(leaf));
+        if (leaf) {
+            postpone_leaf(T, spill);
             if (track) steps++;
         }
         if (RT_DIAG) pc.iters++;
@@ -543,6 +565,10 @@ __device__ __forceinline__ void spec_round(Trav &T, const SceneGPU &sc, SEnt *sp
     if (T.tracing && T.pleaf != REF_NONE) {
         const uint32_t chained = spec_leaf_phase<COUNT, WIDE>(T, sc, spill, cnt);
         if (track) steps += 1u + chained;
+        if (T.tracing && (T.cur & REF_LEAF) && T.cur != REF_NONE) {     // (the leaf phase cleared tracing on REF_NONE)
+            postpone_leaf(T, spill);
+            if (track) steps++;
+        }
     }
     DIAG_ADD(pc.leaf, t1);
 }

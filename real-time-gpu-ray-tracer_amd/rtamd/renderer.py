@@ -150,7 +150,7 @@ class Renderer:
     def timeline(self):
         """Per-wave timeline of the last persistent launch (set_option("timeline", 1) first).
         Structured array: start/end in s_memrealtime ticks (100 MHz), xcc, hw_id, pixels."""
-        w = self.debug_read("timeline").view(np.uint64).reshape(-1, 20)
+        w = self.debug_read("timeline").view(np.uint64).reshape(-1, 24)
         out = np.zeros(len(w), dtype=[("start", np.uint64), ("end", np.uint64), ("xcc", np.uint32),
                                       ("hw_id", np.uint32), ("pixels", np.uint32), ("exhaust", np.uint64),
                                       ("rounds", np.uint32), ("shades", np.uint32), ("grabs", np.uint32),
@@ -158,7 +158,9 @@ class Renderer:
                                       ("cyc_shade", np.uint64), ("iters", np.uint64), ("refill_iters", np.uint64),
                                       ("cyc_lanes", np.uint64), ("cyc_scatter", np.uint64),
                                       ("lanes_interior", np.uint64), ("lanes_leaf_tlas", np.uint64),
-                                      ("lanes_leaf_blas", np.uint64), ("lanes_shade", np.uint64)])
+                                      ("lanes_leaf_blas", np.uint64), ("lanes_shade", np.uint64),
+                                      ("lanes_postpone", np.uint64), ("iters_idle", np.uint64),
+                                      ("hits", np.uint64), ("hits_last_rough", np.uint64)])
         out["start"], out["end"], out["exhaust"] = w[:, 0], w[:, 1], w[:, 4]
         out["xcc"], out["hw_id"], out["pixels"] = w[:, 2] & 0xFFFFFFFF, w[:, 2] >> 32, w[:, 3]
         out["rounds"], out["shades"], out["grabs"] = w[:, 5], w[:, 6], w[:, 7]
@@ -167,6 +169,9 @@ class Renderer:
         out["cyc_lanes"], out["cyc_scatter"] = w[:, 14], w[:, 15]       # diagnostic builds only: lane refill work, scatter sampling
         # diagnostic builds only: lane sums per interior iteration / leaf phase (TLAS, BLAS leaves) / shade step
         out["lanes_interior"], out["lanes_leaf_tlas"], out["lanes_leaf_blas"], out["lanes_shade"] = w[:, 16], w[:, 17], w[:, 18], w[:, 19]
+        # ... lanes postponing a leaf in the interior loop, interior iterations without a node step, shaded hits and
+        # those on a path's last segment with a rough material
+        out["lanes_postpone"], out["iters_idle"], out["hits"], out["hits_last_rough"] = w[:, 20], w[:, 21], w[:, 22], w[:, 23]
         return out
 
     def costmap(self):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-wave timeline of the persistent render kernel (debug option "timeline").
 
-    python scripts/timeline.py [--config C2] [--build sah] [--parts 8] [--out gpurun_out/timeline.npz]
+    python scripts/timeline.py [--config C2] [--build sah] [--out FILE.npz]
 
 Prints the launch span, how long waves live relative to it (a tail / ramp shows up as lifetime
 fraction < 1), start/end spreads and per-XCD pixel shares and finish times.
@@ -55,6 +55,13 @@ def summarize(tl, tag):
             "lanes_per_leaf_phase_tlas_blas": [round(float(tl["lanes_leaf_tlas"].sum() / max(1, tl["rounds"].sum())), 2),
                                                round(float(tl["lanes_leaf_blas"].sum() / max(1, tl["rounds"].sum())), 2)],
             "lanes_per_shade": round(float(tl["lanes_shade"].sum() / max(1, tl["shades"].sum())), 2),
+            # diagnostic builds: the interior loop's totals, the share of its lane-iterations that postponed a leaf, the
+            # share of its iterations without a node step; shaded hits and the share on a path's last rough segment
+            "interior_iters": int(tl["iters"].sum()), "interior_lane_iters": int(tl["lanes_interior"].sum()),
+            "postpone_share_of_lane_iters": round(float(tl["lanes_postpone"].sum() / max(1, tl["lanes_interior"].sum())), 4),
+            "idle_share_of_iters": round(float(tl["iters_idle"].sum() / max(1, tl["iters"].sum())), 4),
+            "hits": int(tl["hits"].sum()),
+            "last_rough_share_of_hits": round(float(tl["hits_last_rough"].sum() / max(1, tl["hits"].sum())), 4),
             "start_us_p50_p99_max": [round(float(np.percentile(st, q)), 1) for q in (50, 99, 100)],
             "end_us_p1_p50_p99": [round(float(np.percentile(en, q)), 1) for q in (1, 50, 99)],
             "pixels": int(tl["pixels"].sum()), "per_xcc": per_xcc}
@@ -64,8 +71,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C2")
     ap.add_argument("--build", default="sah")
-    ap.add_argument("--parts", type=int, nargs="+", default=[1, 8])
-    ap.add_argument("--threshold", type=int, default=8)
     ap.add_argument("--out", default="gpurun_out/timeline.npz")
     ap.add_argument("--opt", action="append", default=[], help="extra scene option key=value")
     ap.add_argument("--pre-opt", action="append", default=[], help="scene option key=value set before the build")
@@ -82,23 +87,20 @@ def main():
         k, v = kv.split("=")
         r.set_option(k, int(v))
     r.build_acceleration_structure(0, mode=a.build).configure_camera(cfg.width, cfg.height)
-    r.set_option("threshold", a.threshold)
     for kv in a.opt:
         k, v = kv.split("=")
         r.set_option(k, int(v))
     saved = {}
-    for parts in a.parts:
-        r.set_option("queue_parts", parts)
-        r.set_option("timeline", 0)
-        for f in range(5):
-            r.render(f, want_rgba=False, rgba8_device=fb.data_ptr(), tiles=tiles)
-        r.set_option("timeline", 1)
-        _, _, stt = r.render(5, want_rgba=False, rgba8_device=fb.data_ptr(), tiles=tiles)
-        tl = r.timeline()
-        saved[f"parts{parts}"] = tl
-        s = summarize(tl, f"parts={parts}")
-        s["kernel_ms_event"] = round(stt["kernel_ms"], 4)
-        print(json.dumps(s), flush=True)
+    r.set_option("timeline", 0)
+    for f in range(5):
+        r.render(f, want_rgba=False, rgba8_device=fb.data_ptr(), tiles=tiles)
+    r.set_option("timeline", 1)
+    _, _, stt = r.render(5, want_rgba=False, rgba8_device=fb.data_ptr(), tiles=tiles)
+    tl = r.timeline()
+    saved["timeline"] = tl
+    s = summarize(tl, a.config)
+    s["kernel_ms_event"] = round(stt["kernel_ms"], 4)
+    print(json.dumps(s), flush=True)
     r.set_option("timeline", 0)
     if tiles:
         np.savez(a.out, **saved)
