@@ -31,8 +31,9 @@ extern "C" {
 /* 2: rt_stats gained update_wait_ms; rt_comm_* / rt_slab_tiles / rt_tile_pixels / rt_scene_detach_comm;
  *    rt_camera_move / rt_frame_pacer_* / rt_comm_set_timeout (round 3)
  * 3: rt_scene_info gained overlap_lanes / stage_depth; "overlap" -1 = library-picked lanes on library streams
- * 4: rt_query_rays */
-#define RT_ABI_VERSION 4u
+ * 4: rt_query_rays
+ * 5: rt_scene_update_triangles_device */
+#define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -164,7 +165,8 @@ typedef enum rt_build_mode {
      * <= 2 instances collapsed into leaves) built by HIP kernels on the scene's stream.  The host
      * still runs the update callback and the instance matrices (Instance.cu:4-17); the TLAS build
      * never blocks the host.  With rt_scene_set_option("rebuild", 1) every BLAS is rebuilt on the
-     * GPU each frame (config C5's per-frame rebuild); rt_scene_update_triangles marks them stale. */
+     * GPU each frame (config C5's per-frame rebuild); rt_scene_update_triangles and
+     * rt_scene_update_triangles_device mark them stale. */
     RT_BUILD_LBVH = 2
 } rt_build_mode;
 
@@ -508,6 +510,61 @@ rt_status rt_scene_collect(rt_scene *scene, rt_stats *accumulated, float *kernel
  * would traverse the old trees while its hits read the new triangles.  Instances keep the local
  * bounds their description supplied (has_local_bounds), as the reference keeps the VTK reader's. */
 rt_status rt_scene_update_triangles(rt_scene *scene, size_t first, size_t count, const rt_triangle *triangles);
+
+/* Triangle updates from device memory: the geometry of triangles [first, first + count) from flat float streams the
+ * caller holds in device memory (a simulation's or a skinning pass's output, a torch tensor), written into the scene
+ * by one kernel (csrc/tri_update.hip) without crossing the host.  RT_BUILD_LBVH scenes only.
+ *
+ * Changes  : only geometry.  Each triangle keeps its material type and index, so nothing read from device memory needs
+ *            validating on the host.  With normals_device the three normals are replaced and has_normals becomes 1.
+ *            Without it normal[] and has_normals stay as they are: a flat triangle (has_normals == 0) gets its normal
+ *            from the new vertices when its leaf record is built, a triangle with stored normals keeps them.
+ * Effect   : that of rt_scene_update_triangles with records that differ from the current ones in exactly those fields.
+ *            The BLASes are rebuilt by the next frame update; until then RT_RENDER_SKIP_UPDATE, rt_trace_rays and
+ *            rt_query_rays return RT_ERR_STATE, as after rt_scene_update_triangles.
+ * Bounds   : instance bounds stay the caller's.  A triangle instance with has_local_bounds == 1 keeps its bounds, as in
+ *            the host path; rt_scene_update_instances replaces them.  The host path recomputes the bounds of a triangle
+ *            instance with has_local_bounds == 0 (a single-primitive instance included) from its triangles; the host
+ *            cannot see the new vertices, so a range that overlaps such an instance returns RT_ERR_UNSUPPORTED, naming
+ *            the first such instance, and nothing is enqueued or changed.
+ * Ordering : the library records an event on `stream`, makes the scene's stream wait for it and writes the triangles
+ *            with one kernel on the scene's stream: behind every BLAS build already enqueued there, exactly where the
+ *            host path's copy sits.  Where traces and query records read the caller's triangles (option
+ *            "cold_records" 0), the kernel also waits for the last frame of every lane and for the queries in flight.
+ *            The library then makes `stream` wait for the kernel's completion event, so the caller may overwrite or
+ *            free its buffers in stream order straight after the call returns, with or without
+ *            RT_TRI_UPDATE_NO_SYNC.  stream NULL: the caller's null stream, ordered with the scene's stream before and
+ *            after the kernel as rt_render and rt_query_rays order device buffers.  Without RT_TRI_UPDATE_NO_SYNC the
+ *            call returns once the write is complete; rt_synchronize and rt_scene_destroy wait for it in any case.
+ *            Host and device updates of one scene take effect in call order.  Nothing on this path waits for the device
+ *            to drain.
+ * Errors   : all before anything is enqueued.  RT_ERR_INVALID_ARGUMENT for a NULL scene or update, a NULL
+ *            vertices_device with count > 0, reserved != 0, unknown flags, a range outside the scene's triangle array,
+ *            or a buffer that hipPointerGetAttributes does not report as accessible from the scene's device;
+ *            RT_ERR_STATE before rt_scene_build; RT_ERR_UNSUPPORTED for a build mode other than RT_BUILD_LBVH and for
+ *            the bounds rule above.  count == 0 returns RT_OK and enqueues nothing.  The caller's current device is
+ *            preserved.  Non-finite vertices are not detected: they behave as they do through the host path.
+ * Rebuilds : rt_scene_build may be called again on a built scene; it then builds from the device-updated triangles
+ *            (the library reads them back once; so does a later rt_scene_update_triangles that has to recompute an
+ *            instance's bounds).
+ * Out of scope: bounds computed on the GPU for instances that derive them from their triangles (they would have to
+ *            reach the per-block instance parameters, the group records and the host mirrors); indexed meshes (gather
+ *            verts[faces] on `stream` first); material changes from device memory; refitting instead of rebuilding. */
+typedef enum rt_triangle_update_flags {
+    RT_TRI_UPDATE_NO_SYNC = 1u << 0   /* return after enqueue */
+} rt_triangle_update_flags;
+
+typedef struct rt_triangle_update {
+    uint64_t first, count;         /* triangles [first, first + count) of the scene's triangle array */
+    const float *vertices_device;  /* 9 floats per triangle: vertex 0, 1, 2, xyz each */
+    const float *normals_device;   /* optional, 9 floats per triangle: normal 0, 1, 2 */
+    uint32_t flags;                /* rt_triangle_update_flags */
+    uint32_t reserved;             /* 0 */
+    void *stream;                  /* hipStream_t the caller produced the buffers on; NULL as rt_query_rays documents */
+} rt_triangle_update;
+/* sizeof(rt_triangle_update) == 48 on LP64 */
+
+rt_status rt_scene_update_triangles_device(rt_scene *scene, const rt_triangle_update *update);
 
 /* Replace instance descriptions [first, first + count) — local bounds / centroid and the transform
  * used when no update callback is set (the next VTK frame's particles, VTKReader.cu:203-215).  The

@@ -1,6 +1,7 @@
 // build.cpp — the acceleration structures: rt_scene_build (instances, their BLASes, the option-"group" BLASes, the
 // leaf-ordered primitive arrays, the frame blocks and per-lane resources), the GPU BLAS builds of RT_BUILD_LBVH and
 // their segment book-keeping, and the geometry updates between frames.
+#include "launch.hpp"
 #include "scene.hpp"
 
 namespace {
@@ -166,6 +167,17 @@ rt_status gpu_build_blas(rt_scene *s) {
     HIP_TRY(s->blas_builder->collapse_wide(s->blas_pairs.p, s->blas_roots.p, s->blas_quads.p, nullptr, s->stream));
     s->blas_dirty = false;
     s->blas_builds++;
+    return RT_OK;
+}
+
+// The host mirror `tris` after rt_scene_update_triangles_device: read raw_tris back once (a cold path: the device is
+// drained).  Called before the mirror's geometry is read: prim_box / prim_centroid, the host builders, the upload
+// of raw_tris by a second rt_scene_build.
+rt_status refresh_tris_mirror(rt_scene *s) {
+    if (!s->tris_host_stale) return RT_OK;
+    RT_TRY(drain(s));
+    HIP_TRY(hipMemcpy(s->tris.data(), s->raw_tris.p, s->tris.size() * sizeof(rt_triangle), hipMemcpyDeviceToHost));
+    s->tris_host_stale = false;
     return RT_OK;
 }
 
@@ -568,6 +580,27 @@ rt_status setup_frame_resources(rt_scene *s) {
     return RT_OK;
 }
 
+// What rt_scene_update_triangles and rt_scene_update_triangles_device check alike: the scene's state, its build mode
+// and the range, overflow-safe.
+rt_status tri_update_check(const rt_scene *s, uint64_t first, uint64_t count) {
+    if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
+    if (s->build_mode != RT_BUILD_LBVH) return fail(RT_ERR_UNSUPPORTED, "triangle updates need RT_BUILD_LBVH");
+    if (first > s->tris.size() || count > s->tris.size() - first) return fail(RT_ERR_INVALID_ARGUMENT, "triangle range out of bounds");
+    return RT_OK;
+}
+
+// ... and what both order their write into raw_tris behind.  No drain: the write goes on the scene stream, behind its
+// pending BLAS builds (the next build, which the frame update enqueues after it, reads the new triangles); with
+// raw_shading() traces read raw_tris at their hits too, so it also waits for every lane's last trace (and the last
+// synchronous one)
+rt_status tri_update_waits(rt_scene *s) {
+    if (!s->raw_shading()) return RT_OK;
+    if (s->r_done) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_done, 0));
+    for (int q = 0; q < rt_scene::NLANE; q++)
+        if (s->r_lane[q]) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_lane[q], 0));
+    return wait_queries(s, s->stream);               // a query's records read raw_tris too (finalize, RAW 1)
+}
+
 }  // namespace
 
 extern "C" {
@@ -578,6 +611,7 @@ rt_status rt_scene_build(rt_scene *s, rt_build_mode mode, uint64_t seed) {
         return fail(RT_ERR_UNSUPPORTED, "unsupported build mode");
     HIP_TRY(hipSetDevice(s->device));
     if (s->built) RT_TRY(drain(s));              // a rebuild frees buffers earlier frames may still read
+    RT_TRY(refresh_tris_mirror(s));              // ... and builds from the triangles a device update wrote
     s->build_seed = seed;
     s->build_mode = mode;
     s->cold_eff = s->cold_records == 1 || (s->cold_records < 0 && !s->rebuild_blas);
@@ -618,17 +652,12 @@ rt_status rt_scene_build(rt_scene *s, rt_build_mode mode, uint64_t seed) {
 
 rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, const rt_triangle *tris) {
     if (!s || (count && !tris)) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
-    if (s->build_mode != RT_BUILD_LBVH) return fail(RT_ERR_UNSUPPORTED, "triangle updates need RT_BUILD_LBVH");
-    if (first > s->tris.size() || count > s->tris.size() - first) return fail(RT_ERR_INVALID_ARGUMENT, "triangle range out of bounds");
+    RT_TRY(tri_update_check(s, first, count));
     if (count == 0) return RT_OK;
     bool ok = true;
     for (size_t k = 0; k < count; k++) material_slot(s, tris[k].material_type, tris[k].material_index, ok);
     if (!ok) return fail(RT_ERR_INVALID_ARGUMENT, "triangle references a material out of range");
     HIP_TRY(hipSetDevice(s->device));
-    // no drain: the copy is ordered behind the scene stream's pending BLAS builds (the next build, which the frame
-    // update enqueues after it, reads the new triangles); with raw_shading() traces read raw_tris at their hits too,
-    // so it also waits for every lane's last trace (and the last synchronous one)
     if (s->ev_raw_staged) RT_TRY(wait_event(s, s->ev_raw_staged));      // the previous staged copy is done
     else HIP_TRY(hipEventCreateWithFlags(&s->ev_raw_staged, hipEventDisableTiming));
     if (count > s->raw_stage_cap) {
@@ -640,12 +669,7 @@ rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, con
     }
     std::memcpy(s->raw_stage, tris, count * sizeof(rt_triangle));
     std::memcpy(s->tris.data() + first, tris, count * sizeof(rt_triangle));
-    if (s->raw_shading()) {
-        if (s->r_done) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_done, 0));
-        for (int q = 0; q < rt_scene::NLANE; q++)
-            if (s->r_lane[q]) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_lane[q], 0));
-        RT_TRY(wait_queries(s, s->stream));          // a query's records read raw_tris too (finalize, RAW 1)
-    }
+    RT_TRY(tri_update_waits(s));
     HIP_TRY(hipMemcpyAsync(s->raw_tris.p + first, s->raw_stage, count * sizeof(rt_triangle), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(extract_tri_verts(s->raw_tris.p, s->raw_verts.p, first, count, s->stream));
     HIP_TRY(hipEventRecord(s->ev_raw_staged, s->stream));
@@ -655,6 +679,7 @@ rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, con
         const rt_instance_desc &id = s->inst_desc[i];
         if (in.ptype != RT_PRIM_TRIANGLE || id.has_local_bounds) continue;
         if ((size_t)in.pindex + in.pcount <= first || in.pindex >= first + count) continue;
+        RT_TRY(refresh_tris_mirror(s));     // after a device update: raw_tris, this call's copy included, read back once
         bounds_from_prims(s, in);
         if (in.pcount == 1) in.centroid = prim_centroid(s, in.ptype, in.pindex);   // not the mean of one: keeps a -0
         instance_update(in, in.x);
@@ -673,6 +698,41 @@ rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, con
     }
     s->blas_dirty = true;
     return RT_OK;
+}
+
+rt_status rt_scene_update_triangles_device(rt_scene *s, const rt_triangle_update *u) {
+    if (!s || !u) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (u->reserved != 0 || (u->flags & ~(uint32_t)RT_TRI_UPDATE_NO_SYNC))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_update_triangles_device: reserved bits set");
+    if (u->count && !u->vertices_device) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    RT_TRY(tri_update_check(s, u->first, u->count));
+    if (u->count == 0) return RT_OK;
+    DeviceRestore restore;
+    HIP_TRY(hipSetDevice(s->device));
+    if (!device_accessible(u->vertices_device, s->device) || (u->normals_device && !device_accessible(u->normals_device, s->device)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_update_triangles_device: a buffer is not accessible from the scene's device");
+    // instance bounds derived from the triangles (rt_scene_update_triangles recomputes them on the host) cannot
+    // follow vertices the host never sees
+    for (size_t i = 0; i < s->inst.size(); i++) {
+        const InstState &in = s->inst[i];
+        if (in.ptype != RT_PRIM_TRIANGLE || s->inst_desc[i].has_local_bounds) continue;
+        if ((uint64_t)in.pindex + in.pcount <= u->first || in.pindex >= u->first + u->count) continue;
+        return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles_device: instance " + std::to_string(i) +
+                                            " derives its bounds from triangles in the range (has_local_bounds == 0)");
+    }
+    if (!s->ev_tri_update) HIP_TRY(hipEventCreateWithFlags(&s->ev_tri_update, hipEventDisableTiming));
+    // scene stream after the caller's (the buffers' producer), the kernel where the host path's copy sits, the
+    // caller's stream after the kernel (the buffers are free again in its order)
+    hipStream_t from = static_cast<hipStream_t>(u->stream);
+    if (from || hipStreamQuery(nullptr) == hipErrorNotReady) RT_TRY(order_after_stream(s, from, s->stream));
+    RT_TRY(tri_update_waits(s));
+    HIP_TRY(launch_tri_update(s->raw_tris.p, s->raw_verts.p, u->vertices_device, u->normals_device, u->first, u->count, s->stream));
+    HIP_TRY(hipEventRecord(s->ev_tri_update, s->stream));
+    HIP_TRY(hipStreamWaitEvent(from, s->ev_tri_update, 0));
+    s->tris_host_stale = true;
+    s->blas_dirty = true;
+    if (u->flags & RT_TRI_UPDATE_NO_SYNC) return RT_OK;
+    return wait_event(s, s->ev_tri_update);
 }
 
 rt_status rt_scene_update_instances(rt_scene *s, size_t first, size_t count, const rt_instance_desc *d) {

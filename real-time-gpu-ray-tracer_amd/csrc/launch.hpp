@@ -1,5 +1,5 @@
 // launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
-// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip) and the host files that call them
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip) and the host files that call them
 // include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
 #pragma once
 
@@ -38,6 +38,10 @@ hipError_t launch_instance_slot_order(const uint32_t *, const InstHot *, const I
                                       hipStream_t);
 hipError_t launch_instance_update(const InstDelta *, uint32_t, InstParams *, uint32_t, InstHot *, InstCold *, float *, float4 *,
                                   const uint32_t *, const TreeRoot *, const uint32_t *, bool, hipStream_t);
+// tri_update.hip: triangles [first, first + count) of raw_tris (vertices, normals if given, has_normals = 1 with them)
+// and raw_verts from flat device streams of 9 floats per triangle
+hipError_t launch_tri_update(rt_triangle *raw_tris, float *raw_verts, const float *vertices, const float *normals,
+                             uint64_t first, uint64_t count, hipStream_t stream);
 
 // One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
 struct TraceFlavour {

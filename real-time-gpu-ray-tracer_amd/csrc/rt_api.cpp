@@ -12,7 +12,7 @@
 //   launch.hpp      the kernel launchers and the EXACT / FAST / fast_math table
 //   scene_sync.cpp  ~rt_scene, drain and the other waits, order_after_null_stream
 //   frame.cpp       frame_update (the host half of a frame), scene_gpu
-//   build.cpp       rt_scene_build, the GPU BLAS builds, rt_scene_update_triangles / _instances
+//   build.cpp       rt_scene_build, the GPU BLAS builds, rt_scene_update_triangles / _triangles_device / _instances
 //   render.cpp      rt_render with auto_lanes and order_null, rt_assemble_tiles, rt_trace_rays, rt_query_rays, rt_box_test
 //   scene_comm.cpp  the RCCL attach / detach / abort path and a frame's gather
 //   debug.cpp       rt_scene_debug_read, rt_scene_export_blas / _tlas

@@ -339,6 +339,11 @@ struct rt_scene {
     rt_triangle *raw_stage = nullptr;
     size_t raw_stage_cap = 0;
     hipEvent_t ev_raw_staged = nullptr;            // the last staged copy finished (raw_stage reusable)
+    // rt_scene_update_triangles_device: its kernel's completion (the caller's stream waits on it; the scene stream
+    // orders everything else), and whether `tris` still mirrors raw_tris: the kernel's vertices and normals never
+    // reach the host, so whoever reads the mirror's geometry first calls refresh_tris_mirror (build.cpp)
+    hipEvent_t ev_tri_update = nullptr;
+    bool tris_host_stale = false;
     DevBuf<rt_sphere> raw_sph;
     DevBuf<rt_parallelogram> raw_quad;
     DevBuf<TreeRoot> blas_roots;        // per segment the builder holds (seg_of_blas)
@@ -440,6 +445,7 @@ rt_status wait_if_pending(hipStream_t st, hipEvent_t ev, bool *pending);
 rt_status wait_queries(rt_scene *s, hipStream_t st);
 rt_status wait_blas_built(rt_scene *s, hipStream_t st);
 rt_status wait_frame_block(rt_scene *s);
+rt_status order_after_stream(rt_scene *s, hipStream_t from, hipStream_t st);
 rt_status order_after_null_stream(rt_scene *s, hipStream_t st);
 
 // frame.cpp
@@ -456,6 +462,7 @@ rt_status lbvh_segments(rt_scene *s);
 rt_status lbvh_sync_groups(rt_scene *s);
 rt_status gpu_build_blas(rt_scene *s);
 rt_status gpu_setup_blas(rt_scene *s, const uint32_t *slot_count);
+rt_status refresh_tris_mirror(rt_scene *s);
 
 // scene_comm.cpp: a multi-GPU frame's gather to rank 0 and its assembly there, on the trace's stream
 rt_status comm_gather(rt_scene *s, int q, uint8_t *frame_out, hipStream_t stream);

@@ -43,6 +43,7 @@ rt_scene::~rt_scene() {
     if (ev_caller) (void)hipEventDestroy(ev_caller);
     if (ev_blas_built) (void)hipEventDestroy(ev_blas_built);
     if (ev_raw_staged) (void)hipEventDestroy(ev_raw_staged);
+    if (ev_tri_update) (void)hipEventDestroy(ev_tri_update);
     if (raw_stage) (void)hipHostFree(raw_stage);
     for (int i = 0; i < NSTAGE; i++)
         if (staging[i]) (void)hipHostFree(staging[i]);
@@ -164,9 +165,13 @@ rt_status wait_blas_built(rt_scene *s, hipStream_t st) {
 
 // Order stream `st` after what the caller enqueued on the null stream before the call: the scene's streams are
 // non-blocking, which HIP does not order with it (rt_render explains when a caller expects that order).
-rt_status order_after_null_stream(rt_scene *s, hipStream_t st) {
+rt_status order_after_null_stream(rt_scene *s, hipStream_t st) { return order_after_stream(s, nullptr, st); }
+
+// Order stream `st` after what is enqueued on the caller's stream `from` now (ev_caller serves every such hand-over: a
+// wait takes the record it finds, so the event may be recorded again straight after).
+rt_status order_after_stream(rt_scene *s, hipStream_t from, hipStream_t st) {
     if (!s->ev_caller) HIP_TRY(hipEventCreateWithFlags(&s->ev_caller, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(s->ev_caller, nullptr));
+    HIP_TRY(hipEventRecord(s->ev_caller, from));
     HIP_TRY(hipStreamWaitEvent(st, s->ev_caller, 0));
     return RT_OK;
 }

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-RT_ABI_VERSION = 4
+RT_ABI_VERSION = 5
 
 RT_OK = 0
 RT_STATUS_NAMES = {
@@ -33,6 +33,8 @@ RT_RENDER_KEEP_COUNTERS = 1 << 4
 RT_QUERY_EXACT = 1 << 0
 RT_QUERY_ANY_HIT = 1 << 1
 RT_QUERY_NO_SYNC = 1 << 2
+
+RT_TRI_UPDATE_NO_SYNC = 1 << 0
 
 MISS = 0xFFFFFFFF
 
@@ -130,6 +132,14 @@ class RayQuery(C.Structure):
                 ("t_device", C.c_void_p), ("occluded_device", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class TriangleUpdate(C.Structure):
+    """rt_triangle_update: triangle range, device vertex / normal streams and stream of one
+    rt_scene_update_triangles_device call."""
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("vertices_device", C.c_void_p),
+                ("normals_device", C.c_void_p), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("stream", C.c_void_p)]
+
+
 class SceneInfo(C.Structure):
     _fields_ = [("blas_count", C.c_uint64), ("blas_node_pairs", C.c_uint64),
                 ("blas_leaves", C.c_uint64), ("tlas_node_pairs", C.c_uint64),
@@ -180,7 +190,7 @@ EXPORTED_SYMBOLS = (
     "rt_vtk_series_read", "rt_vtk_series_count", "rt_vtk_series_entry", "rt_vtk_series_free",
     "rt_comm_unique_id", "rt_scene_attach_comm", "rt_scene_detach_comm", "rt_slab_tiles", "rt_tile_pixels",
     "rt_comm_set_timeout", "rt_camera_control_init", "rt_camera_move", "rt_clock_ns", "rt_frame_pace",
-    "rt_box_test", "rt_query_rays",
+    "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -230,6 +240,8 @@ def _declare(lib):
     lib.rt_scene_debug_read.restype = C.c_int
     lib.rt_scene_update_triangles.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
     lib.rt_scene_update_triangles.restype = C.c_int
+    lib.rt_scene_update_triangles_device.argtypes = [C.c_void_p, P(TriangleUpdate)]
+    lib.rt_scene_update_triangles_device.restype = C.c_int
     lib.rt_scene_update_instances.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, P(InstanceDesc)]
     lib.rt_scene_update_instances.restype = C.c_int
     lib.rt_vtk_read.argtypes = [C.c_char_p, P(C.c_void_p)]

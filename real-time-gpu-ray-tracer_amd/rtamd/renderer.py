@@ -12,6 +12,7 @@ There is no CPU fallback: constructing a Renderer without librtamd.so or without
 from __future__ import annotations
 
 import ctypes as C
+import sys
 from contextlib import nullcontext as _null_context
 
 import numpy as np
@@ -87,6 +88,51 @@ class Renderer:
         """Replace triangles [first, first + len) (scenes.TRIANGLE_DTYPE array); "lbvh" scenes only."""
         t = np.ascontiguousarray(triangles)
         abi.check(self.lib, self.lib.rt_scene_update_triangles(self.h, first, t.shape[0], t.ctypes.data))
+        return self
+
+    def update_triangles_device(self, first: int, vertices, normals=None, stream=None, sync: bool = True):
+        """rt_scene_update_triangles_device: the geometry of triangles [first, first + n) from device memory; "lbvh"
+        scenes only.  vertices (and optionally normals): 9 floats per triangle, either an object with data_ptr() — a
+        torch tensor: float32, contiguous, numel() == 9 n, on the scene's device — or a (device pointer, n) tuple.
+        Materials stay; without normals each triangle keeps its normals (a flat one follows its new vertices).
+        stream: the stream the buffers were produced on, a raw hipStream_t or an object with .cuda_stream (None =
+        torch's current stream when torch is loaded, else the null stream).  With sync=False the call returns after
+        the enqueue; the buffers may be overwritten in stream order either way."""
+        def stream_of(x, name):
+            if isinstance(x, tuple):
+                ptr, n = x
+                return int(ptr or 0), int(n)
+            if not hasattr(x, "data_ptr"):
+                raise ValueError(f"{name}: a tensor with data_ptr() or a (pointer, triangle count) tuple")
+            if str(x.dtype) != "torch.float32":
+                raise ValueError(f"{name}: float32, not {x.dtype}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+            dev = x.device
+            if dev.type != "cuda" or (dev.index if dev.index is not None else 0) != self.device:
+                raise ValueError(f"{name}: on {dev}, the scene is on cuda:{self.device}")
+            if x.numel() % 9:
+                raise ValueError(f"{name}: 9 floats per triangle, not {x.numel()} in all")
+            return (x.data_ptr() if x.numel() else 0), x.numel() // 9
+
+        vptr, n = stream_of(vertices, "vertices")
+        nptr = 0
+        if normals is not None:
+            nptr, nn = stream_of(normals, "normals")
+            if nn != n:
+                raise ValueError(f"normals: {nn} triangles, vertices hold {n}")
+        if stream is None:
+            torch = sys.modules.get("torch")       # never imported here: `import rtamd` needs no torch
+            if torch is not None and torch.cuda.is_available():
+                stream = torch.cuda.current_stream(self.device)
+        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+        u = abi.TriangleUpdate()
+        u.first, u.count = first, n
+        u.vertices_device = vptr or None
+        u.normals_device = nptr or None
+        u.flags = 0 if sync else abi.RT_TRI_UPDATE_NO_SYNC
+        u.stream = raw or None
+        abi.check(self.lib, self.lib.rt_scene_update_triangles_device(self.h, C.byref(u)))
         return self
 
     def update_instances(self, first: int, instances):

@@ -121,10 +121,30 @@ class VtkSeriesPlayer:
         self.entries = read_series(series_path)
         self.first_instance = first_instance
 
+        self._device = None                       # preload(): per entry (vertices, normals, instances)
+
     def __len__(self):
         return len(self.entries)
 
+    def preload(self, device="cuda"):
+        """Convert every entry once and keep its vertices and normals as torch tensors on `device` (the scene's):
+        load(k) then hands them over with rt_scene_update_triangles_device and no triangle crosses the host again.
+        The particle instances carry their own bounds (has_local_bounds), as that call requires."""
+        import torch                              # here: `import rtamd` needs no torch
+        self._device = []
+        for path, _ in self.entries:
+            tris, inst = VtkFile(path).convert(0)
+            verts = torch.from_numpy(np.ascontiguousarray(tris["vertex"]).reshape(-1)).to(device)
+            norms = torch.from_numpy(np.ascontiguousarray(tris["normal"]).reshape(-1)).to(device)
+            self._device.append((verts, norms, inst))
+        return self
+
     def load(self, k: int):
+        if self._device is not None:
+            verts, norms, inst = self._device[k]
+            self.r.update_triangles_device(0, verts, norms)
+            self.r.update_instances(self.first_instance, inst)
+            return self.entries[k][1]
         tris, inst = VtkFile(self.entries[k][0]).convert(0)
         self.r.update_triangles(0, tris)
         self.r.update_instances(self.first_instance, inst)
