@@ -26,8 +26,10 @@
 //            (round 6) cost C2 4.4 % and C3 2.5 % per frame through register pressure alone;
 //   XD_ALL : every decision inside the slabs' error margin, every box test of a ray with a parallel axis and (pair
 //            order) every comparison of two entry t's inside the margin re-taken with the reference's slab: the traversal
-//            takes the reference's decisions.  The binary pairs and mode 3 — FAST then equals EXACT on the same trees
-//            (tests/test_gpu_parity_full.py: the reference's trees, and C5's benched LBVH trees with "exact_decisions").
+//            takes the reference's decisions; and every leaf that is hit gets the reference's entry t (slab_ref_near), so
+//            that its re-test at the pop is the reference's too (traverse.hpp, pop_keep).  The binary pairs and mode 3 —
+//            FAST then equals EXACT on the same trees (tests/test_gpu_parity_full.py: the reference's trees, and C5's
+//            benched LBVH trees with "exact_decisions"; tests/test_gpu_xform_edges.py: surfaces 1e-6 apart).
 //            For mode 2 by default it cost C5 +34 % per frame (sibling boxes' entry t's often tie exactly:
 //            profiles/r06/exact_decisions/).
 constexpr int XD_CULL = 0, XD_ALL = 2;
@@ -100,6 +102,21 @@ struct BoxArgs { float b[6]; f3 o, d; float tmax; };
 __device__ __attribute__((noinline)) float slab_ref_entry(BoxArgs a) {
     float te = 0.0f;
     return slab_ref(a.b, a.o, a.d, TMIN, a.tmax, te) ? te : __builtin_nanf("");
+}
+// The entry t of the reference's slab alone (cur.min after the three axes, BoundingBox.cu:34-72), for a box the
+// reference accepts.  Per axis min(t1, t2) is the nearer plane's distance, and which plane that is follows from the
+// sign of d: IEEE subtraction and division are monotone, so t1 <= t2 for d > 0 and t2 <= t1 for d < 0 (equal values
+// where they tie).  A parallel axis leaves cur.min alone.  Three divisions instead of the slab's six.
+__device__ __forceinline__ float slab_ref_near(const float *b, const f3 &o, const f3 &d) {
+    float cmin = TMIN;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const float dd = comp(d, a);
+        if (fabsf(dd) < FZERO) continue;
+        const float t = fdiv((dd > 0.0f ? b[2 * a] : b[2 * a + 1]) - comp(o, a), dd);
+        if (t > cmin) cmin = t;
+    }
+    return cmin;
 }
 // A FAST box decision: each end of the interval [lo, hi] (hi includes tmax) is within |pad| + 2^-20 |t| of the
 // reference's (lo, hi >= TMIN > 0 wherever lo < hi can hold), so the widened test cons_lo(lo) < cons_hi(hi) keeps every
@@ -237,6 +254,19 @@ __device__ __forceinline__ void quad_decide(const float4 *Q, const float4 &lx, c
                     pa = j == 4 ? te : pa;
                     pb = j == 5 ? te : pb;
                 }
+            }
+        }
+        if (XB == XD_ALL) {    // a leaf that is hit carries the reference's entry t to its re-test at the pop (pop_keep)
+            uint32_t lm = (h[0] && (R.x & REF_LEAF) ? 1u : 0u) | (h[1] && (R.y & REF_LEAF) ? 2u : 0u) |
+                          (h[2] && (R.z & REF_LEAF) ? 4u : 0u) | (h[3] && (R.w & REF_LEAF) ? 8u : 0u);
+#pragma unroll 1
+            for (; lm; lm &= lm - 1u) {
+                const int j = __builtin_ctz(lm);
+                float b[6];
+#pragma unroll
+                for (int c = 0; c < 6; c++) b[c] = comp4(Q[c], j);
+                const float te = slab_ref_near(b, r.o, r.d);
+                t[0] = j == 0 ? te : t[0]; t[1] = j == 1 ? te : t[1]; t[2] = j == 2 ? te : t[2]; t[3] = j == 3 ? te : t[3];
             }
         }
     }

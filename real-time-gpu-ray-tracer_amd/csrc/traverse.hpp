@@ -31,9 +31,15 @@ struct Trav {
 // A popped entry (or the speculative successor) survives its re-test: the reference re-runs the box test with the
 // current tmax, which accepts it iff its entry t < tmax (the exit side passed at the push and tmax only shrinks).
 // FAST (conservative slabs): the entry is widened by its ray's bound first (a BLAS entry belongs to the current
-// instance's ray).
+// instance's ray).  An interior node kept that the reference culls costs box tests only: its children's entries are
+// not below its own, and their tests see the same tmax.  A leaf kept that the reference culls is entered without
+// another box test, and a primitive in it within 1e-6 beyond tmax (Range.cuh:33-43) replaces the hit.  So the
+// exact-decision instances (XD_ALL) give every leaf the reference's own entry t where it is hit (pair_test,
+// quad_decide) and compare that one as the reference does.
+template <int XB = XD_CULL>
 __device__ __forceinline__ bool pop_keep(const Trav &T, float tn, uint32_t ref) {
 #if !RT_EXACT
+    if (XB == XD_ALL && (ref & REF_LEAF)) return tn < T.tmax;
     return cons_lo(tn, (ref & REF_BLAS) ? T.lr.pad : T.wr.pad) < T.tmax;
 #else
     (void)ref;
@@ -91,6 +97,15 @@ __device__ __forceinline__ uint4 pair_test(const Trav &T, const SceneGPU &sc, ui
     const RayP &r = blas ? T.lr : T.wr;
     h0 = slab<XB>(b0, r, TMIN, T.tmax, e0);
     h1 = slab<XB>(b1, r, TMIN, T.tmax, e1);
+#if !RT_EXACT
+    if (XB == XD_ALL) {   // a leaf that is hit carries the reference's entry t to its re-test at the pop (pop_keep)
+        // ... and where both children are hit, both entries: the callers order them by e0 > e1, which must compare two
+        // values of one kind (siblings often share their near plane, and then tie in the reference)
+        const bool l0 = h0 && (D.x & REF_LEAF), l1 = h1 && (D.y & REF_LEAF);
+        if (l0 || (l1 && h0)) e0 = slab_ref_near(b0, r.o, r.d);
+        if (l1 || (l0 && h1)) e1 = slab_ref_near(b1, r.o, r.d);
+    }
+#endif
     return D;
 }
 
@@ -162,7 +177,7 @@ __device__ __forceinline__ void trav_step(Trav &T, const SceneGPU &sc, SEnt *spi
     // pop until an entry survives the re-test (entry t < tmax)
     while (!T.stk.empty()) {
         const SEnt e = stack_pop(T.stk, spill);
-        if (pop_keep(T, __uint_as_float(e.tn), e.ref)) { T.cur = e.ref; return; }
+        if (pop_keep<XB>(T, __uint_as_float(e.tn), e.ref)) { T.cur = e.ref; return; }
     }
     T.tracing = false;
 }
@@ -185,19 +200,21 @@ __device__ __forceinline__ void trav_step(Trav &T, const SceneGPU &sc, SEnt *spi
 // the leaf phase when the re-tested successor is one — not in an iteration of its own: no leaf runs between the two
 // places, so tmax, every pop_keep decision and the lane's operations and their order are the same, and a lane
 // takes one interior iteration less per leaf.
+template <int XB>
 __device__ __forceinline__ void pop_next(Trav &T, const SEnt *spill) {
     while (!T.stk.empty()) {
         const SEnt e = stack_pop(T.stk, spill);
         const float tn = __uint_as_float(e.tn);
-        if (pop_keep(T, tn, e.ref)) { T.cur = e.ref; T.curT = tn; return; }
+        if (pop_keep<XB>(T, tn, e.ref)) { T.cur = e.ref; T.curT = tn; return; }
     }
     T.cur = REF_NONE;
 }
 // The leaf in cur (a real ref: REF_NONE carries the leaf bit too) waits in pleaf for the leaf phase; the lane goes on
 // with the next entry.  T.tracing stays set while pleaf is, whatever cur becomes.
+template <int XB>
 __device__ __forceinline__ void postpone_leaf(Trav &T, const SEnt *spill) {
     T.pleaf = T.cur;
-    pop_next(T, spill);
+    pop_next<XB>(T, spill);
 }
 
 // One interior-loop step of a lane whose cur is an interior node.
@@ -309,7 +326,7 @@ __device__ __forceinline__ void wide_interior_step(Trav &T, const SceneGPU &sc, 
         float t0 = h[0] ? t[0] : inf, t1 = h[1] ? t[1] : inf, t2 = h[2] ? t[2] : inf, t3 = h[3] ? t[3] : inf;
         uint32_t r0 = R.x, r1 = R.y, r2 = R.z, r3 = R.w;
         const uint32_t nh = (uint32_t)h[0] + (uint32_t)h[1] + (uint32_t)h[2] + (uint32_t)h[3];
-        if (nh == 0) { pop_next(T, spill); return; }
+        if (nh == 0) { pop_next<XB>(T, spill); return; }
         // sort the 4 (t, ref) ascending; misses (t = inf) sink to the end
         cswap(t0, r0, t1, r1); cswap(t2, r2, t3, r3); cswap(t0, r0, t2, r2); cswap(t1, r1, t3, r3); cswap(t1, r1, t2, r2);
         // the 1..3 far hits go to the three LDS slots above the top without branching on their count (farthest
@@ -330,7 +347,7 @@ __device__ __forceinline__ void wide_interior_step(Trav &T, const SceneGPU &sc, 
         return;
     }
     const uint32_t na = (uint32_t)h[0] + (uint32_t)h[1], nb = (uint32_t)h[2] + (uint32_t)h[3];
-    if (na + nb == 0) { pop_next(T, spill); return; }
+    if (na + nb == 0) { pop_next<XB>(T, spill); return; }
     // The reference's visit order (BLAS.cu:186-202: push far, visit near, the right child first iff tLeft > tRight):
     // inside each half its two slots, then the halves by their boxes' entry t.  A missed slot counts as t = +inf, so
     // it is second in its half, and a half without hits goes second; the hits then come first in each half.
@@ -386,7 +403,7 @@ __device__ __forceinline__ void spec_interior_step(Trav &T, const SceneGPU &sc, 
         T.curT = h0 ? e0 : e1;
         return;
     }
-    pop_next(T, spill);
+    pop_next<XBOX(WIDE)>(T, spill);
 }
 
 // Process the postponed leaf, then resume at cur (re-tested) — TLAS.cu:157-173 / BLAS.cu:153-176.
@@ -430,14 +447,14 @@ __device__ __forceinline__ uint32_t spec_leaf_phase(Trav &T, const SceneGPU &sc,
                 T.curT = te;
                 if (RT_CHAIN_ROOT_LEAF && (T.cur & REF_LEAF)) { leaf = T.cur; chained = true; }
             } else {
-                pop_next(T, spill);
+                pop_next<XBOX(WIDE)>(T, spill);
             }
         } else
 #endif
         {
             const InstHot &I = sc.inst_hot[T.cur_inst];
             if (enter_instance<XBOX(WIDE)>(T, I.inv, I.root_box, te)) { T.cur = WIDE ? I.root_ref_wide : I.root_ref; T.curT = te; }
-            else pop_next(T, spill);
+            else pop_next<XBOX(WIDE)>(T, spill);
         }
     }
     if (leaf & REF_BLAS) {                  // the postponed BLAS leaf, or (chained) the entered BLAS's root leaf
@@ -483,8 +500,9 @@ __device__ __forceinline__ uint32_t spec_leaf_phase(Trav &T, const SceneGPU &sc,
                 if (h) accept(T, t, type, slot, u, v);
             }
         }
-        if (chained) pop_next(T, spill);                                   // the root leaf is done
-        else if (T.cur != REF_NONE && !pop_keep(T, T.curT, T.cur)) pop_next(T, spill);   // re-test the successor
+        if (chained) pop_next<XBOX(WIDE)>(T, spill);                       // the root leaf is done
+        else if (T.cur != REF_NONE && !pop_keep<XBOX(WIDE)>(T, T.curT, T.cur))     // re-test the successor
+            pop_next<XBOX(WIDE)>(T, spill);
     }
     if (T.cur == REF_NONE) T.tracing = false;
     return chained ? 1u : 0u;
@@ -551,7 +569,7 @@ __device__ __forceinline__ void spec_round(Trav &T, const SceneGPU &sc, SEnt *sp
         const bool leaf = active && T.pleaf == REF_NONE && (T.cur & REF_LEAF) && T.cur != REF_NONE;
         if (RT_DIAG) pc.lanes_postpone += (unsigned long long)__popcll(__ballot(leaf));
         if (leaf) {
-            postpone_leaf(T, spill);
+            postpone_leaf<XBOX(WIDE)>(T, spill);
             if (track) steps++;
         }
         if (RT_DIAG) pc.iters++;
@@ -566,7 +584,7 @@ __device__ __forceinline__ void spec_round(Trav &T, const SceneGPU &sc, SEnt *sp
         const uint32_t chained = spec_leaf_phase<COUNT, WIDE>(T, sc, spill, cnt);
         if (track) steps += 1u + chained;
         if (T.tracing && (T.cur & REF_LEAF) && T.cur != REF_NONE) {     // (the leaf phase cleared tracing on REF_NONE)
-            postpone_leaf(T, spill);
+            postpone_leaf<XBOX(WIDE)>(T, spill);
             if (track) steps++;
         }
     }
