@@ -32,7 +32,8 @@ extern "C" {
  *    rt_camera_move / rt_frame_pacer_* / rt_comm_set_timeout (round 3)
  * 3: rt_scene_info gained overlap_lanes / stage_depth; "overlap" -1 = library-picked lanes on library streams
  * 4: rt_query_rays
- * 5: rt_scene_update_triangles_device */
+ * 5: rt_scene_update_triangles_device
+ *    (RT_TRI_UPDATE_BOUNDS arrived within 5: a flag value that was rejected before is accepted now) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -522,11 +523,34 @@ rt_status rt_scene_update_triangles(rt_scene *scene, size_t first, size_t count,
  * Effect   : that of rt_scene_update_triangles with records that differ from the current ones in exactly those fields.
  *            The BLASes are rebuilt by the next frame update; until then RT_RENDER_SKIP_UPDATE, rt_trace_rays and
  *            rt_query_rays return RT_ERR_STATE, as after rt_scene_update_triangles.
- * Bounds   : instance bounds stay the caller's.  A triangle instance with has_local_bounds == 1 keeps its bounds, as in
- *            the host path; rt_scene_update_instances replaces them.  The host path recomputes the bounds of a triangle
- *            instance with has_local_bounds == 0 (a single-primitive instance included) from its triangles; the host
- *            cannot see the new vertices, so a range that overlaps such an instance returns RT_ERR_UNSUPPORTED, naming
- *            the first such instance, and nothing is enqueued or changed.
+ * Bounds   : without RT_TRI_UPDATE_BOUNDS instance bounds stay the caller's.  A triangle instance with
+ *            has_local_bounds == 1 keeps its bounds, as in the host path; rt_scene_update_instances replaces them.  The
+ *            host path recomputes the bounds of a triangle instance with has_local_bounds == 0 (a single-primitive
+ *            instance included) from its triangles; the host cannot see the new vertices, so a range that overlaps
+ *            such an instance returns RT_ERR_UNSUPPORTED, naming the first such instance, and nothing is enqueued or
+ *            changed.
+ *            With RT_TRI_UPDATE_BOUNDS the device derives them, and that refusal does not apply.  Every triangle
+ *            instance whose primitive range overlaps [first, first + count) becomes device-bounded, whatever its
+ *            has_local_bounds, single-primitive instances included (spheres and parallelograms never).  From the next
+ *            frame update on — the one that rebuilds the BLASes from the new triangles — its local box is the union of
+ *            its triangles' boxes and its local centroid the mean of their centroids over its whole primitive range,
+ *            the rules of the host path (one triangle keeps its own centroid).  The box is a min / max and so exact
+ *            (where two extremes are -0 and +0 only their value is promised); the centroid is (float)(S / count) with
+ *            S a double-precision sum in a fixed shape that depends on count alone (csrc/inst_bounds_map.hpp): two
+ *            runs give the same bits, and they are the host path's whenever the host's sequential sum is exact, else
+ *            within one float ulp of them.  The centroid only feeds the TLAS build, so hits depend on it through the
+ *            tree's shape alone.
+ *            A device-bounded instance goes back to host bounds by rt_scene_update_instances on it (the description's
+ *            bounds with has_local_bounds == 1, else derived from the triangles, read back once; a group it belongs
+ *            to breaks, as always), by rt_scene_build (has_local_bounds == 1 instances return to their description's
+ *            bounds, the others get bounds derived from the triangles read back), and by a host
+ *            rt_scene_update_triangles whose range touches it or a group that holds a device-bounded member: that call
+ *            reads the triangles back once and derives those instances' bounds on the host.
+ *            A later device update without the flag leaves a device-bounded instance device-bounded: its box follows
+ *            the rebuilt BLAS, its centroid stays that of the last flagged update.
+ *            Option "group": a group with a device-bounded member is device-bounded itself: while it is intact its box
+ *            is the union over all its members' triangles, its centroid the mean of its members' centroids.  The flag
+ *            never breaks a group; a broken group's members are ordinary instances with BLASes of their own.
  * Ordering : the library records an event on `stream`, makes the scene's stream wait for it and writes the triangles
  *            with one kernel on the scene's stream: behind every BLAS build already enqueued there, exactly where the
  *            host path's copy sits.  Where traces and query records read the caller's triangles (option
@@ -537,21 +561,23 @@ rt_status rt_scene_update_triangles(rt_scene *scene, size_t first, size_t count,
  *            after the kernel as rt_render and rt_query_rays order device buffers.  Without RT_TRI_UPDATE_NO_SYNC the
  *            call returns once the write is complete; rt_synchronize and rt_scene_destroy wait for it in any case.
  *            Host and device updates of one scene take effect in call order.  Nothing on this path waits for the device
- *            to drain.
+ *            to drain.  RT_TRI_UPDATE_BOUNDS adds kernels behind that one on the scene's stream; they wait for the
+ *            instance-record updates of frames already enqueued (microseconds), never for a trace.
  * Errors   : all before anything is enqueued.  RT_ERR_INVALID_ARGUMENT for a NULL scene or update, a NULL
  *            vertices_device with count > 0, reserved != 0, unknown flags, a range outside the scene's triangle array,
  *            or a buffer that hipPointerGetAttributes does not report as accessible from the scene's device;
- *            RT_ERR_STATE before rt_scene_build; RT_ERR_UNSUPPORTED for a build mode other than RT_BUILD_LBVH and for
- *            the bounds rule above.  count == 0 returns RT_OK and enqueues nothing.  The caller's current device is
- *            preserved.  Non-finite vertices are not detected: they behave as they do through the host path.
+ *            RT_ERR_STATE before rt_scene_build; RT_ERR_UNSUPPORTED for a build mode other than RT_BUILD_LBVH and,
+ *            without RT_TRI_UPDATE_BOUNDS, for the bounds rule above; with it, for an instance in the range that shares
+ *            its BLAS (same first primitive) with an instance of another primitive count.  count == 0 returns RT_OK and
+ *            enqueues nothing.  The caller's current device is preserved.  Non-finite vertices are not detected: they behave as they do through the host path.
  * Rebuilds : rt_scene_build may be called again on a built scene; it then builds from the device-updated triangles
  *            (the library reads them back once; so does a later rt_scene_update_triangles that has to recompute an
  *            instance's bounds).
- * Out of scope: bounds computed on the GPU for instances that derive them from their triangles (they would have to
- *            reach the per-block instance parameters, the group records and the host mirrors); indexed meshes (gather
- *            verts[faces] on `stream` first); material changes from device memory; refitting instead of rebuilding. */
+ * Out of scope: device-derived bounds for spheres and parallelograms; indexed meshes (gather verts[faces] on `stream`
+ *            first); material changes from device memory; refitting instead of rebuilding. */
 typedef enum rt_triangle_update_flags {
-    RT_TRI_UPDATE_NO_SYNC = 1u << 0   /* return after enqueue */
+    RT_TRI_UPDATE_NO_SYNC = 1u << 0,  /* return after enqueue */
+    RT_TRI_UPDATE_BOUNDS = 1u << 1    /* derive the bounds of the instances the range overlaps on the device */
 } rt_triangle_update_flags;
 
 typedef struct rt_triangle_update {

@@ -181,6 +181,47 @@ rt_status refresh_tris_mirror(rt_scene *s) {
     return RT_OK;
 }
 
+// RT_TRI_UPDATE_BOUNDS (inst_bounds.hip), at rt_scene_build: the static tables — an instance's primitives never
+// change — the partial sums, and every record's local centroid as the host holds it.  No record is device-bounded.
+rt_status setup_inst_bounds(rt_scene *s) {
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    const size_t n = s->inst.size() + s->groups.size();
+    s->dev_bounded.assign(n, 0);
+    s->ib_entry_of.assign(s->inst.size(), NONE);
+    std::vector<InstBoundsEntry> table;
+    std::vector<uint32_t> chunk_inst, multi, members;
+    std::vector<uint2> groups;
+    for (size_t i = 0; i < s->inst.size(); i++) {
+        const InstState &in = s->inst[i];
+        if (in.ptype != RT_PRIM_TRIANGLE) continue;
+        s->ib_entry_of[i] = (uint32_t)table.size();
+        const uint32_t nc = ib_chunks(in.pcount);
+        if (nc > 1) multi.push_back((uint32_t)table.size());
+        table.push_back(InstBoundsEntry{in.pindex, in.pcount, (uint32_t)chunk_inst.size(), (uint32_t)i});
+        chunk_inst.insert(chunk_inst.end(), nc, (uint32_t)table.size() - 1);
+    }
+    for (const InstGroup &G : s->groups) {
+        groups.push_back(make_uint2((uint32_t)members.size(), (uint32_t)G.members.size()));
+        for (uint32_t m : G.members) members.push_back(s->ib_entry_of[m]);       // groups hold triangle instances only
+    }
+    RT_TRY(upload(s->ib_table, table));
+    RT_TRY(upload(s->ib_chunk_inst, chunk_inst));
+    RT_TRY(upload(s->ib_multi, multi));
+    RT_TRY(upload(s->ib_groups, groups));
+    RT_TRY(upload(s->ib_members, members));
+    RT_TRY(alloc_buf(s->ib_partials, 3 * chunk_inst.size()));
+    std::vector<float4> cent(n);
+    for (size_t i = 0; i < n; i++) {
+        const hm::V3 c = record_state(s, i).centroid;
+        cent[i] = make_float4(c.x, c.y, c.z, 0.0f);
+    }
+    RT_TRY(upload(s->ib_cent, cent));
+    if (s->ib_cent_stage) HIP_TRY(hipHostFree(s->ib_cent_stage));
+    s->ib_cent_stage = nullptr;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->ib_cent_stage), (n ? n : 1) * sizeof(float4), hipHostMallocDefault));
+    return RT_OK;
+}
+
 // RT_BUILD_LBVH: upload the raw primitives, allocate the leaf-ordered arrays, build every BLAS once.
 rt_status gpu_setup_blas(rt_scene *s, const uint32_t *slot_count) {
     const std::vector<LbvhSeg> &segs = s->lbvh_segs;
@@ -580,6 +621,36 @@ rt_status setup_frame_resources(rt_scene *s) {
     return RT_OK;
 }
 
+bool tri_range_overlaps(const InstState &in, uint64_t first, uint64_t count) {
+    return in.ptype == RT_PRIM_TRIANGLE && (uint64_t)in.pindex + in.pcount > first && in.pindex < first + count;
+}
+
+// RT_TRI_UPDATE_BOUNDS: the host changed the local centroids of `records` (sorted): their entries of the device array,
+// which a group's mean reads, on the scene stream — through the pinned stage, after the record chains of the frames
+// already enqueued (a chain may still read the device-written value of a record the host just took back)
+rt_status refresh_dev_centroids(rt_scene *s, const std::vector<uint32_t> &records) {
+    if (records.empty() || !s->ib_cent.p) return RT_OK;
+    RT_TRY(wait_record_chains(s, s->stream));
+    for (size_t k = 0; k < records.size();) {
+        size_t e = k;
+        while (e + 1 < records.size() && records[e + 1] == records[e] + 1) e++;
+        for (size_t j = k; j <= e; j++) {
+            const hm::V3 c = record_state(s, records[j]).centroid;
+            s->ib_cent_stage[records[j]] = make_float4(c.x, c.y, c.z, 0.0f);
+        }
+        HIP_TRY(hipMemcpyAsync(s->ib_cent.p + records[k], s->ib_cent_stage + records[k], (e - k + 1) * sizeof(float4),
+                               hipMemcpyHostToDevice, s->stream));
+        k = e + 1;
+    }
+    return RT_OK;
+}
+
+// an instance's bounds as rt_scene_update_triangles derives them from the (current) host mirror
+void host_bounds(rt_scene *s, InstState &in) {
+    bounds_from_prims(s, in);
+    if (in.pcount == 1) in.centroid = prim_centroid(s, in.ptype, in.pindex);   // not the mean of one: keeps a -0
+}
+
 // What rt_scene_update_triangles and rt_scene_update_triangles_device check alike: the scene's state, its build mode
 // and the range, overflow-safe.
 rt_status tri_update_check(const rt_scene *s, uint64_t first, uint64_t count) {
@@ -640,6 +711,8 @@ rt_status rt_scene_build(rt_scene *s, rt_build_mode mode, uint64_t seed) {
     RT_TRY(upload(s->materials, mats));
     layout_frame_block(s);
     RT_TRY(setup_gpu_tlas(s));
+    s->dev_bounded.clear();                      // the descriptions' or the host-derived bounds again
+    if (mode == RT_BUILD_LBVH) RT_TRY(setup_inst_bounds(s));
     RT_TRY(setup_frame_resources(s));
     s->active = -1;
 
@@ -673,20 +746,37 @@ rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, con
     HIP_TRY(hipMemcpyAsync(s->raw_tris.p + first, s->raw_stage, count * sizeof(rt_triangle), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(extract_tri_verts(s->raw_tris.p, s->raw_verts.p, first, count, s->stream));
     HIP_TRY(hipEventRecord(s->ev_raw_staged, s->stream));
-    // instance boxes derived from the triangles (RenderPin.cu:124-139); VTK-style bounds stay as given
+    // instance boxes derived from the triangles (RenderPin.cu:124-139); VTK-style bounds stay as given.  A
+    // device-bounded instance in the range, or in a group with a member in the range, comes back to the host: its
+    // bounds from the mirror, read back first (RT_TRI_UPDATE_BOUNDS)
+    const size_t ni = s->inst.size();
+    std::vector<uint8_t> back(s->dev_bounded.empty() ? 0 : ni, 0);
+    for (size_t g = 0; g < s->groups.size() && !back.empty(); g++) {
+        const InstGroup &G = s->groups[g];
+        if (!s->dev_bounded[ni + g]) continue;
+        bool touched = false;
+        for (uint32_t m : G.members) touched = touched || tri_range_overlaps(s->inst[m], first, count);
+        if (!touched) continue;
+        for (uint32_t m : G.members) back[m] = s->dev_bounded[m];
+        s->dev_bounded[ni + g] = 0;
+    }
+    std::vector<uint32_t> changed;                     // group members whose centroid the host changed
     for (size_t i = 0; i < s->inst.size(); i++) {
         InstState &in = s->inst[i];
         const rt_instance_desc &id = s->inst_desc[i];
-        if (in.ptype != RT_PRIM_TRIANGLE || id.has_local_bounds) continue;
-        if ((size_t)in.pindex + in.pcount <= first || in.pindex >= first + count) continue;
+        const bool in_range = tri_range_overlaps(in, first, count);
+        const bool take_back = !back.empty() && (back[i] || (s->dev_bounded[i] && in_range));
+        if (!take_back && (!in_range || id.has_local_bounds)) continue;
         RT_TRY(refresh_tris_mirror(s));     // after a device update: raw_tris, this call's copy included, read back once
-        bounds_from_prims(s, in);
-        if (in.pcount == 1) in.centroid = prim_centroid(s, in.ptype, in.pindex);   // not the mean of one: keeps a -0
+        host_bounds(s, in);
         instance_update(in, in.x);
+        if (take_back) s->dev_bounded[i] = 0;
         if (s->gpu_tlas()) s->inst_dirty[i] = rt_scene::ALL_BLOCKS;     // the GPU copies of its local box
+        if (s->group_of[i]) changed.push_back((uint32_t)i);
     }
     for (size_t g = 0; g < s->groups.size(); g++) {   // option "group" (LBVH): the union of the members' boxes
         InstGroup &G = s->groups[g];
+        if (!s->dev_bounded.empty() && s->dev_bounded[ni + g]) continue;       // the device's, untouched by this range
         double c[3] = {0, 0, 0};
         for (size_t k = 0; k < G.members.size(); k++) {
             const InstState &m = s->inst[G.members[k]];
@@ -696,13 +786,14 @@ rt_status rt_scene_update_triangles(rt_scene *s, size_t first, size_t count, con
         G.st.centroid = hm::v3((float)(c[0] / G.members.size()), (float)(c[1] / G.members.size()), (float)(c[2] / G.members.size()));
         if (s->gpu_tlas()) s->inst_dirty[s->inst.size() + g] = rt_scene::ALL_BLOCKS;
     }
+    RT_TRY(refresh_dev_centroids(s, changed));
     s->blas_dirty = true;
     return RT_OK;
 }
 
 rt_status rt_scene_update_triangles_device(rt_scene *s, const rt_triangle_update *u) {
     if (!s || !u) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (u->reserved != 0 || (u->flags & ~(uint32_t)RT_TRI_UPDATE_NO_SYNC))
+    if (u->reserved != 0 || (u->flags & ~(uint32_t)(RT_TRI_UPDATE_NO_SYNC | RT_TRI_UPDATE_BOUNDS)))
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_update_triangles_device: reserved bits set");
     if (u->count && !u->vertices_device) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
     RT_TRY(tri_update_check(s, u->first, u->count));
@@ -711,14 +802,23 @@ rt_status rt_scene_update_triangles_device(rt_scene *s, const rt_triangle_update
     HIP_TRY(hipSetDevice(s->device));
     if (!device_accessible(u->vertices_device, s->device) || (u->normals_device && !device_accessible(u->normals_device, s->device)))
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_update_triangles_device: a buffer is not accessible from the scene's device");
+    const bool bounds = (u->flags & RT_TRI_UPDATE_BOUNDS) != 0;
     // instance bounds derived from the triangles (rt_scene_update_triangles recomputes them on the host) cannot
-    // follow vertices the host never sees
-    for (size_t i = 0; i < s->inst.size(); i++) {
+    // follow vertices the host never sees, unless the device derives them (RT_TRI_UPDATE_BOUNDS)
+    for (size_t i = 0; i < s->inst.size() && !bounds; i++) {
         const InstState &in = s->inst[i];
         if (in.ptype != RT_PRIM_TRIANGLE || s->inst_desc[i].has_local_bounds) continue;
         if ((uint64_t)in.pindex + in.pcount <= u->first || in.pindex >= u->first + u->count) continue;
         return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles_device: instance " + std::to_string(i) +
                                             " derives its bounds from triangles in the range (has_local_bounds == 0)");
+    }
+    // a device-bounded instance's box is its BLAS's root: the BLAS must hold exactly the instance's triangles (instances
+    // with one first primitive share a BLAS whatever their counts)
+    for (size_t i = 0; i < s->inst.size() && bounds; i++) {
+        const InstState &in = s->inst[i];
+        if (!tri_range_overlaps(in, u->first, u->count) || s->lbvh_segs[in.blas].count == in.pcount) continue;
+        return fail(RT_ERR_UNSUPPORTED, "rt_scene_update_triangles_device: instance " + std::to_string(i) +
+                                            " shares the BLAS of an instance with another primitive count");
     }
     if (!s->ev_tri_update) HIP_TRY(hipEventCreateWithFlags(&s->ev_tri_update, hipEventDisableTiming));
     // scene stream after the caller's (the buffers' producer), the kernel where the host path's copy sits, the
@@ -729,6 +829,25 @@ rt_status rt_scene_update_triangles_device(rt_scene *s, const rt_triangle_update
     HIP_TRY(launch_tri_update(s->raw_tris.p, s->raw_verts.p, u->vertices_device, u->normals_device, u->first, u->count, s->stream));
     HIP_TRY(hipEventRecord(s->ev_tri_update, s->stream));
     HIP_TRY(hipStreamWaitEvent(from, s->ev_tri_update, 0));
+    if (bounds) {
+        // every triangle instance the range overlaps, and its group, is device-bounded from the next frame update on:
+        // that update rebuilds the BLASes (their roots are the boxes) behind these kernels on the scene stream, and
+        // every record chain waits for that build.  The centroid array is shared by all frame blocks, so the kernels
+        // wait for the chains already enqueued; nothing here waits for a trace or for the device to drain
+        const size_t ni = s->inst.size();
+        for (size_t i = 0; i < ni; i++) {
+            if (!tri_range_overlaps(s->inst[i], u->first, u->count)) continue;
+            if (!s->dev_bounded[i]) { s->dev_bounded[i] = 1; s->inst_dirty[i] = rt_scene::ALL_BLOCKS; }
+            if (!s->group_of[i]) continue;
+            const size_t gr = ni + s->group_of[i] - 1;             // its group's record
+            if (!s->dev_bounded[gr]) { s->dev_bounded[gr] = 1; s->inst_dirty[gr] = rt_scene::ALL_BLOCKS; }
+        }
+        RT_TRY(wait_record_chains(s, s->stream));
+        const InstBoundsGPU ib{s->ib_table.p, s->ib_chunk_inst.p, s->ib_multi.p, s->ib_groups.p, s->ib_members.p,
+                               (uint32_t)s->ib_chunk_inst.n, (uint32_t)s->ib_multi.n, (uint32_t)s->ib_groups.n, (uint32_t)ni,
+                               s->ib_partials.p, s->ib_cent.p};
+        HIP_TRY(launch_inst_bounds(ib, s->raw_verts.p, u->first, u->count, s->stream));
+    }
     s->tris_host_stale = true;
     s->blas_dirty = true;
     if (u->flags & RT_TRI_UPDATE_NO_SYNC) return RT_OK;
@@ -753,7 +872,11 @@ rt_status rt_scene_update_instances(rt_scene *s, size_t first, size_t count, con
             in.box = hm::Box::from_ranges({d[k].local_bounds[0], d[k].local_bounds[1]}, {d[k].local_bounds[2], d[k].local_bounds[3]},
                                           {d[k].local_bounds[4], d[k].local_bounds[5]});
             in.centroid = hm::of(d[k].local_centroid);
+        } else if (!s->dev_bounded.empty() && s->dev_bounded[i]) {            // back from the device: the mirror, read back
+            RT_TRY(refresh_tris_mirror(s));
+            host_bounds(s, in);
         }
+        if (!s->dev_bounded.empty()) s->dev_bounded[i] = 0;                   // RT_TRI_UPDATE_BOUNDS ends here
         instance_update(in, d[k].xform);
         if (s->gpu_tlas()) s->inst_dirty[i] = rt_scene::ALL_BLOCKS;
         // option "group": the group's box and transform were taken at the build; its members go back to

@@ -103,6 +103,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
             }
             in.box.store(d.p.box);
             d.p.pad[0] = record_inactive(s, i) ? 1.0f : 0.0f;
+            d.p.pad[1] = !s->dev_bounded.empty() && s->dev_bounded[i] ? 1.0f : 0.0f;   // RT_TRI_UPDATE_BOUNDS
         }
         uint8_t *fd = s->frame_dev[b];
         uint32_t live = 0;                              // records in this frame's TLAS
@@ -131,7 +132,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
                                        s->inst_params.p + (size_t)b * n, n,
                                        reinterpret_cast<InstHot *>(fd + s->off_hot), reinterpret_cast<InstCold *>(fd + s->off_cold),
                                        reinterpret_cast<float *>(fd + s->off_tbox), reinterpret_cast<float4 *>(fd + s->off_tcent),
-                                       s->inst_blas.p, s->blas_roots.p, s->blas_wide_refs.p, /*inf_inactive=*/!small, cs));
+                                       s->inst_blas.p, s->blas_roots.p, s->blas_wide_refs.p, s->ib_cent.p, /*inf_inactive=*/!small, cs));
         s->chain_stream[b] = cs;
         if (small) {
             // one workgroup: the LBVH TLAS over the live records, quads, slots, slot-ordered records (lbvh_tlas_small.hpp)

@@ -41,16 +41,20 @@ __device__ __forceinline__ void rows(float *dst, const hm::Mat &m) {   // rows 1
 // live only in HBM; wide_refs: the quad roots of host-built BLASes under a GPU TLAS, null for GPU-built ones).
 // inf_inactive: an inactive record's box is all +inf (the multi-kernel TLAS builder sorts it into a subtree no ray
 // enters); else its real box is kept and only the centroid's w marks it (the one-workgroup builder skips it)
-struct RootPatch { const uint32_t *inst_blas; const TreeRoot *roots; const uint32_t *wide_refs; };
+// dev_cent (RT_TRI_UPDATE_BOUNDS): a device-bounded record (InstParams::pad[1] != 0) takes its local box from that
+// root — the exact union of its triangles' boxes — and its local centroid from dev_cent (inst_bounds.hip), not from
+// its parameters; every other record computes as without it
+struct RootPatch { const uint32_t *inst_blas; const TreeRoot *roots; const uint32_t *wide_refs; const float4 *dev_cent; };
 __global__ __launch_bounds__(256) void instance_update_kernel(const InstParams *__restrict__ params, uint32_t n,
                                                               InstHot *__restrict__ hot, InstCold *__restrict__ cold,
                                                               float *__restrict__ tbox, float4 *__restrict__ tcent,
                                                               RootPatch rp, bool inf_inactive) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
+    TreeRoot R{};
     if (rp.inst_blas) {
         const uint32_t b = rp.inst_blas[i];
-        const TreeRoot R = rp.roots[b];
+        R = rp.roots[b];
 #pragma unroll
         for (int k = 0; k < 6; k++) hot[i].root_box[k] = R.box[k];
         hot[i].root_ref = R.ref;
@@ -68,7 +72,13 @@ __global__ __launch_bounds__(256) void instance_update_kernel(const InstParams *
     // the local box exactly as the host holds it (already volume-expanded): from_points would not move it
     hm::Box lb;
     for (int a = 0; a < 3; a++) lb.r[a] = hm::Range{P.box[2 * a], P.box[2 * a + 1]};
-    const hm::V3 tc = hm::apply_point(fwd, hm::V3{P.centroid[0], P.centroid[1], P.centroid[2]});
+    hm::V3 lc{P.centroid[0], P.centroid[1], P.centroid[2]};
+    if (P.pad[1] != 0.0f && rp.inst_blas && rp.dev_cent) {   // device-bounded record
+        for (int a = 0; a < 3; a++) lb.r[a] = hm::Range{R.box[2 * a], R.box[2 * a + 1]};
+        const float4 dc = rp.dev_cent[i];
+        lc = hm::V3{dc.x, dc.y, dc.z};
+    }
+    const hm::V3 tc = hm::apply_point(fwd, lc);
     if (P.pad[0] != 0.0f && inf_inactive) {   // inactive record (an intact group's member, a broken group)
         const float inf = __builtin_huge_valf();
 #pragma unroll
@@ -105,7 +115,8 @@ hipError_t launch_instance_slot_order(const uint32_t *slots, const InstHot *hot,
 // deltas: `count` changed instances (device memory: the uploaded part of the frame block)
 hipError_t launch_instance_update(const InstDelta *deltas, uint32_t count, InstParams *params, uint32_t n, InstHot *hot,
                                   InstCold *cold, float *tbox, float4 *tcent, const uint32_t *inst_blas,
-                                  const TreeRoot *roots, const uint32_t *wide_refs, bool inf_inactive, hipStream_t stream) {
+                                  const TreeRoot *roots, const uint32_t *wide_refs, const float4 *dev_cent, bool inf_inactive,
+                                  hipStream_t stream) {
     if (count) {
         hipLaunchKernelGGL(instance_apply_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, deltas, count, params, n);
         const hipError_t e = hipGetLastError();
@@ -113,7 +124,7 @@ hipError_t launch_instance_update(const InstDelta *deltas, uint32_t count, InstP
     }
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(instance_update_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, params, n, hot, cold, tbox, tcent,
-                       RootPatch{inst_blas, roots, wide_refs}, inf_inactive);
+                       RootPatch{inst_blas, roots, wide_refs, dev_cent}, inf_inactive);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
-// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip) and the host files that call them
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip) and the host files that call them
 // include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
 #pragma once
 
@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/rt.h"
+#include "inst_bounds_map.hpp"
 #include "layout.hpp"
 
 namespace rtamd {
@@ -36,12 +37,27 @@ hipError_t launch_schedule(uint32_t *, uint32_t *, uint32_t *, uint32_t *, uint3
                            uint32_t, uint32_t, void *, const void *, size_t, unsigned long long *, hipStream_t);
 hipError_t launch_instance_slot_order(const uint32_t *, const InstHot *, const InstCold *, uint32_t, InstHot *, InstCold *,
                                       hipStream_t);
+// dev_cent: the device-bounded records' local centroids (inst_bounds.hip), read for records with InstParams::pad[1] set
 hipError_t launch_instance_update(const InstDelta *, uint32_t, InstParams *, uint32_t, InstHot *, InstCold *, float *, float4 *,
-                                  const uint32_t *, const TreeRoot *, const uint32_t *, bool, hipStream_t);
+                                  const uint32_t *, const TreeRoot *, const uint32_t *, const float4 *dev_cent, bool, hipStream_t);
 // tri_update.hip: triangles [first, first + count) of raw_tris (vertices, normals if given, has_normals = 1 with them)
 // and raw_verts from flat device streams of 9 floats per triangle
 hipError_t launch_tri_update(rt_triangle *raw_tris, float *raw_verts, const float *vertices, const float *normals,
                              uint64_t first, uint64_t count, hipStream_t stream);
+// inst_bounds.hip (RT_TRI_UPDATE_BOUNDS): the static tables of rt_scene_build and the arrays the kernels write.  The
+// local centroid of every triangle instance that [first, first + count) overlaps, over the instance's whole range,
+// and of every group with such a member, into cent[record]
+struct InstBoundsGPU {
+    const InstBoundsEntry *table;      // the triangle instances
+    const uint32_t *chunk_inst;        // work item -> table index
+    const uint32_t *multi;             // table indices of the instances of more than one chunk
+    const uint2 *groups;               // per group {first member, members} into `members`
+    const uint32_t *members;           // table indices, in member order
+    uint32_t chunks, n_multi, n_groups, n_inst;
+    double *partials;                  // 3 per work item
+    float4 *cent;                      // one per record: instances, then groups
+};
+hipError_t launch_inst_bounds(const InstBoundsGPU &b, const float *raw_verts, uint64_t first, uint64_t count, hipStream_t stream);
 
 // One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
 struct TraceFlavour {

@@ -142,6 +142,7 @@ struct alignas(16) InstParams {     // 96 B
     float box[6];                   // local box {xmin,xmax,ymin,ymax,zmin,zmax} (volume-expanded, as the host holds it)
     float centroid[3];              // local centroid
     float pad[3];                   // pad[0] != 0: inactive record (kept out of the GPU TLAS, option "group")
+                                    // pad[1] != 0: device-bounded record (RT_TRI_UPDATE_BOUNDS): box and centroid above unused
 };
 static_assert(sizeof(InstParams) == 96, "InstParams must be 96 B");
 struct alignas(16) InstDelta {      // 112 B

@@ -22,6 +22,7 @@
 #include "devbuf.hpp"
 #include "error.hpp"
 #include "host_math.hpp"
+#include "inst_bounds_map.hpp"
 #include "layout.hpp"
 #include "lbvh.hpp"
 
@@ -344,6 +345,20 @@ struct rt_scene {
     // reach the host, so whoever reads the mirror's geometry first calls refresh_tris_mirror (build.cpp)
     hipEvent_t ev_tri_update = nullptr;
     bool tris_host_stale = false;
+    // RT_TRI_UPDATE_BOUNDS (inst_bounds.hip): per record (instances, then groups) whether the device holds its local
+    // bounds — the box is its BLAS root's, the centroid dev_cent's — until the host takes them back
+    // (rt_scene_update_instances, a host rt_scene_update_triangles on it, rt_scene_build); the host's InstState::box /
+    // centroid of such a record are stale.  The static tables of the build (InstBoundsGPU, launch.hpp); ib_cent holds
+    // every record's local centroid, the host-bounded ones' uploaded at the build and whenever the host changes one
+    // that a group's mean reads (refresh_dev_centroids, through the pinned ib_cent_stage, slot = record)
+    std::vector<uint8_t> dev_bounded;
+    std::vector<uint32_t> ib_entry_of;  // instance -> entry of ib_table (NONE: not a triangle instance)
+    DevBuf<InstBoundsEntry> ib_table;
+    DevBuf<uint32_t> ib_chunk_inst, ib_multi, ib_members;
+    DevBuf<uint2> ib_groups;
+    DevBuf<double> ib_partials;
+    DevBuf<float4> ib_cent;
+    float4 *ib_cent_stage = nullptr;
     DevBuf<rt_sphere> raw_sph;
     DevBuf<rt_parallelogram> raw_quad;
     DevBuf<TreeRoot> blas_roots;        // per segment the builder holds (seg_of_blas)
@@ -447,6 +462,7 @@ rt_status wait_blas_built(rt_scene *s, hipStream_t st);
 rt_status wait_frame_block(rt_scene *s);
 rt_status order_after_stream(rt_scene *s, hipStream_t from, hipStream_t st);
 rt_status order_after_null_stream(rt_scene *s, hipStream_t st);
+rt_status wait_record_chains(rt_scene *s, hipStream_t st);
 
 // frame.cpp
 void instance_update(InstState &in, const rt_xform &x);
@@ -463,6 +479,7 @@ rt_status lbvh_sync_groups(rt_scene *s);
 rt_status gpu_build_blas(rt_scene *s);
 rt_status gpu_setup_blas(rt_scene *s, const uint32_t *slot_count);
 rt_status refresh_tris_mirror(rt_scene *s);
+rt_status setup_inst_bounds(rt_scene *s);
 
 // scene_comm.cpp: a multi-GPU frame's gather to rank 0 and its assembly there, on the trace's stream
 rt_status comm_gather(rt_scene *s, int q, uint8_t *frame_out, hipStream_t stream);

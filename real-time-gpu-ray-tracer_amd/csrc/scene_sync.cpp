@@ -33,6 +33,9 @@ rt_scene::~rt_scene() {
     raw_tris.release(); raw_verts.release(); raw_sph.release(); raw_quad.release(); blas_roots.release(); inst_blas.release();
     blas_wide_refs.release();
     gpu_counts.release(); inst_params.release();
+    ib_table.release(); ib_chunk_inst.release(); ib_multi.release(); ib_members.release(); ib_groups.release();
+    ib_partials.release(); ib_cent.release();
+    if (ib_cent_stage) (void)hipHostFree(ib_cent_stage);
     for (BlasSet &sp : spare) sp.release();
     for (int q = 0; q < NLANE; q++) {
         if (ev_blas_lane[q]) (void)hipEventDestroy(ev_blas_lane[q]);
@@ -160,6 +163,19 @@ rt_status wait_blas_built(rt_scene *s, hipStream_t st) {
     bool pending;
     RT_TRY(wait_if_pending(st, s->ev_blas_built, &pending));
     if (!pending) s->blas_build_done = s->blas_build_seq;
+    return RT_OK;
+}
+
+// Order stream `st` after the record chains (instance update + TLAS build: microseconds, not the traces) of the GPU-built
+// frames already enqueued on other streams: ev_copied[b] is recorded behind block b's chain.  What rewrites data every
+// block's chain reads — the device-bounded centroids (RT_TRI_UPDATE_BOUNDS) — waits for them; a chain that has
+// finished needs no wait (a host query).
+rt_status wait_record_chains(rt_scene *s, hipStream_t st) {
+    for (int b = 0; b < rt_scene::NLANE; b++) {
+        if (!s->chain_stream[b] || s->chain_stream[b] == st || !s->ev_copied[b]) continue;
+        bool pending;
+        RT_TRY(wait_if_pending(st, s->ev_copied[b], &pending));
+    }
     return RT_OK;
 }
 

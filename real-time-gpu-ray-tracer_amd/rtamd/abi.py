@@ -35,6 +35,7 @@ RT_QUERY_ANY_HIT = 1 << 1
 RT_QUERY_NO_SYNC = 1 << 2
 
 RT_TRI_UPDATE_NO_SYNC = 1 << 0
+RT_TRI_UPDATE_BOUNDS = 1 << 1
 
 MISS = 0xFFFFFFFF
 

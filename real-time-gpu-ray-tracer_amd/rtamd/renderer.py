@@ -90,14 +90,17 @@ class Renderer:
         abi.check(self.lib, self.lib.rt_scene_update_triangles(self.h, first, t.shape[0], t.ctypes.data))
         return self
 
-    def update_triangles_device(self, first: int, vertices, normals=None, stream=None, sync: bool = True):
+    def update_triangles_device(self, first: int, vertices, normals=None, stream=None, sync: bool = True,
+                                bounds: bool = False):
         """rt_scene_update_triangles_device: the geometry of triangles [first, first + n) from device memory; "lbvh"
         scenes only.  vertices (and optionally normals): 9 floats per triangle, either an object with data_ptr() — a
         torch tensor: float32, contiguous, numel() == 9 n, on the scene's device — or a (device pointer, n) tuple.
         Materials stay; without normals each triangle keeps its normals (a flat one follows its new vertices).
         stream: the stream the buffers were produced on, a raw hipStream_t or an object with .cuda_stream (None =
         torch's current stream when torch is loaded, else the null stream).  With sync=False the call returns after
-        the enqueue; the buffers may be overwritten in stream order either way."""
+        the enqueue; the buffers may be overwritten in stream order either way.  bounds=True (RT_TRI_UPDATE_BOUNDS):
+        the device derives the local bounds of every triangle instance the range overlaps, so instances without
+        bounds of their own are accepted and a mesh may leave the bounds it was built with."""
         def stream_of(x, name):
             if isinstance(x, tuple):
                 ptr, n = x
@@ -130,7 +133,7 @@ class Renderer:
         u.first, u.count = first, n
         u.vertices_device = vptr or None
         u.normals_device = nptr or None
-        u.flags = 0 if sync else abi.RT_TRI_UPDATE_NO_SYNC
+        u.flags = (0 if sync else abi.RT_TRI_UPDATE_NO_SYNC) | (abi.RT_TRI_UPDATE_BOUNDS if bounds else 0)
         u.stream = raw or None
         abi.check(self.lib, self.lib.rt_scene_update_triangles_device(self.h, C.byref(u)))
         return self

@@ -122,14 +122,17 @@ class VtkSeriesPlayer:
         self.first_instance = first_instance
 
         self._device = None                       # preload(): per entry (vertices, normals, instances)
+        self._derive_bounds = False               # preload(derive_bounds=True)
 
     def __len__(self):
         return len(self.entries)
 
-    def preload(self, device="cuda"):
+    def preload(self, device="cuda", derive_bounds: bool = False):
         """Convert every entry once and keep its vertices and normals as torch tensors on `device` (the scene's):
         load(k) then hands them over with rt_scene_update_triangles_device and no triangle crosses the host again.
-        The particle instances carry their own bounds (has_local_bounds), as that call requires."""
+        The particle instances carry their own bounds (has_local_bounds), as that call requires without its bounds
+        flag.  derive_bounds=True: load(k) passes bounds=True instead of calling rt_scene_update_instances, so the
+        device derives the particles' bounds from the new triangles and an option-"group" group stays one TLAS item."""
         import torch                              # here: `import rtamd` needs no torch
         self._device = []
         for path, _ in self.entries:
@@ -137,11 +140,15 @@ class VtkSeriesPlayer:
             verts = torch.from_numpy(np.ascontiguousarray(tris["vertex"]).reshape(-1)).to(device)
             norms = torch.from_numpy(np.ascontiguousarray(tris["normal"]).reshape(-1)).to(device)
             self._device.append((verts, norms, inst))
+        self._derive_bounds = bool(derive_bounds)
         return self
 
     def load(self, k: int):
         if self._device is not None:
             verts, norms, inst = self._device[k]
+            if self._derive_bounds:
+                self.r.update_triangles_device(0, verts, norms, bounds=True)
+                return self.entries[k][1]
             self.r.update_triangles_device(0, verts, norms)
             self.r.update_instances(self.first_instance, inst)
             return self.entries[k][1]

@@ -6,8 +6,13 @@ one process, alternating the three and repeating each --reps times after warm-up
 
   (a) rt_scene_update_triangles over all particle triangles from a host array;
   (b) rt_scene_update_triangles_device with normals over the same range;
+  (b') (b) with RT_TRI_UPDATE_BOUNDS: the device also derives the particle instances' bounds (csrc/inst_bounds.hip reads
+      36 B per triangle more).  The library releases the caller's stream behind the write kernel, before those kernels,
+      so events on that stream do not see them: (b') is timed on the host clock, against "b_wall";
   (c) a plain device-to-device hipMemcpyAsync (torch copy_) that moves the bytes (b) must move, read plus write:
       72 B read + 112 B written per triangle = a copy of 92 B per triangle.  The yardstick for (b)'s kernel.
+  (d) what per-frame bounds cost without the flag: (b) plus rt_scene_update_instances for every particle instance
+      (descriptions prepared once), host clock.  It runs last, after the frames: it breaks the particles' group for good.
 
 (b) and (c) are timed by events on the caller's stream around the call (the library makes that stream wait for its
 kernel, so the stop event falls behind it).  (a) has no device bracket: most of it is host work (the material walk, two
@@ -15,7 +20,8 @@ memcpys) before its copy reaches the scene's stream, so (a) is timed on the host
 return, and so is (b) a second time ("b_wall") to compare the two in one measure.
 
 Then frames with the per-frame rebuild, pipelined on the library's lanes as bench.py's, each frame preceded by (a) or
-by (b) without waiting: ms per frame on the host clock over --frames frames.
+by (b) without waiting: ms per frame on the host clock over --frames frames; then --pairs alternating pairs of such
+runs with (b') and with (b) ("frame_pairs_ms").
 
 Each step runs under a time limit of its own (--step-timeout seconds, SIGALRM): a step that exceeds it ends the
 process.  Prints one JSON line per step and a summary line."""
@@ -63,12 +69,15 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--pairs", type=int, default=4)
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--pre-opt", action="append", default=[], help="rt_scene_set_option key=value before the build")
     a = ap.parse_args()
+    import ctypes as C
+
     import numpy as np
     import torch
-    from rtamd import Renderer, scenes
+    from rtamd import Renderer, abi, scenes
 
     cfg = scenes.CONFIGS[a.config]
     n_p = cfg.particles * 1024
@@ -86,6 +95,8 @@ def main():
         norms = torch.from_numpy(np.ascontiguousarray(tris["normal"]).reshape(-1)).cuda()
         copy_src = torch.empty(92 * n_p, dtype=torch.uint8, device="cuda")
         copy_dst = torch.empty_like(copy_src)
+        first_inst = len(scene.instances) - cfg.particles
+        inst_descs = scenes.instance_desc_array(scene.instances[first_inst:])
         frame_bufs = [torch.zeros(cfg.width * cfg.height * 4, dtype=torch.uint8, device="cuda") for _ in range(8)]
         st = torch.cuda.Stream()
         torch.cuda.synchronize()
@@ -104,9 +115,9 @@ def main():
         r.synchronize()
         return (time.perf_counter() - t0) * 1e3
 
-    def device_update_wall():
+    def device_update_wall(bounds=False):
         t0 = time.perf_counter()
-        r.update_triangles_device(0, verts, norms, stream=st)
+        r.update_triangles_device(0, verts, norms, stream=st, bounds=bounds)
         r.synchronize()
         return (time.perf_counter() - t0) * 1e3
 
@@ -114,11 +125,19 @@ def main():
         with torch.cuda.stream(st):
             copy_dst.copy_(copy_src, non_blocking=True)
 
-    ms = {"a_host_wall": [], "b_device_events": [], "b_device_wall": [], "c_memcpy_events": []}
+    def device_plus_instances_wall():
+        t0 = time.perf_counter()
+        r.update_triangles_device(0, verts, norms, stream=st, sync=False)
+        abi.check(r.lib, r.lib.rt_scene_update_instances(r.h, first_inst, cfg.particles, inst_descs))
+        r.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    ms = {"a_host_wall": [], "b_device_events": [], "b2_device_bounds_wall": [], "b_device_wall": [], "c_memcpy_events": []}
     with step("updates", a.step_timeout):
         for k in range(a.warmup + a.reps):
             row = {"a_host_wall": host_update(),
                    "b_device_events": timed_on_stream(lambda: r.update_triangles_device(0, verts, norms, stream=st, sync=False)),
+                   "b2_device_bounds_wall": device_update_wall(bounds=True),
                    "c_memcpy_events": timed_on_stream(memcpy),
                    "b_device_wall": device_update_wall()}
             r.synchronize()
@@ -146,13 +165,29 @@ def main():
     with step("frames_no_update", a.step_timeout):
         frame_ms["none"] = round(frames(lambda: None), 4)
 
+    pairs = {"b2_device_bounds": [], "b_device": []}
+    with step("frame_pairs", a.step_timeout):
+        for _ in range(a.pairs):
+            pairs["b2_device_bounds"].append(round(frames(
+                lambda: r.update_triangles_device(0, verts, norms, stream=st, sync=False, bounds=True)), 4))
+            pairs["b_device"].append(round(frames(
+                lambda: r.update_triangles_device(0, verts, norms, stream=st, sync=False)), 4))
+    ms["d_device_plus_instances_wall"] = []
+    with step("device_plus_instances", a.step_timeout):
+        for k in range(a.warmup + a.reps):
+            v = device_plus_instances_wall()
+            if k >= a.warmup:
+                ms["d_device_plus_instances_wall"].append(v)
+
     out = {"config": a.config, "opts": a.pre_opt, "triangles": n_p, "update_ms": {k: spread(v) for k, v in ms.items()},
-           "bytes_moved_b": 184 * n_p, "frame_ms": frame_ms, "frames": a.frames,
+           "bytes_moved_b": 184 * n_p, "frame_ms": frame_ms, "frame_pairs_ms": pairs, "frames": a.frames,
            "device": torch.cuda.get_device_name(0)}
     b, c = out["update_ms"]["b_device_events"]["median"], out["update_ms"]["c_memcpy_events"]["median"]
     out["b_GBps"] = round(184 * n_p / (b * 1e6), 1)
     out["c_GBps"] = round(184 * n_p / (c * 1e6), 1)
     out["b_over_c"] = round(b / c, 3)
+    out["b2_minus_b_wall_ms"] = round(out["update_ms"]["b2_device_bounds_wall"]["median"] -
+                                      out["update_ms"]["b_device_wall"]["median"], 4)
     print(json.dumps(out), flush=True)
     r.cleanup()
 
