@@ -15,6 +15,19 @@
 // tmax[i] instead of +inf (trav_init's tmax argument), so every box and primitive test sees the caller's bound exactly
 // as it sees the closest hit so far.  !(tmax > TMIN), NaN included, is a miss without traversal.
 //
+// Closest, tmax that grows: Range::inRange is closed with a 1e-6 window (Range.cuh:33-43), so a primitive up to 1e-6
+// BEYOND the closest hit so far is accepted and becomes the new tmax: the range's upper end does not only shrink, and
+// spec_round's argument that a decision taken ahead of a postponed leaf is made good by its re-test (traverse.hpp,
+// above pop_next) needs that it does.  Where a box has a corner on a vertex several triangles share, its entry t
+// equals the hit's t and "entry t < tmax" depends on the moment it is asked: a pop ahead of the leaf that raises tmax
+// drops a node for good, and an entry pushed ahead of a leaf passes its re-test only because a later leaf raised tmax
+// (DESIGN §3.3).  While no leaf phase leaves a lane's tmax larger than it found it, every such decision was taken with
+// a tmax no smaller than the reference's and re-tested with one no larger, and the argument holds.  So a lane watches
+// its tmax from round to round (a round runs at most one BLAS leaf per lane), and a ray whose tmax grew is traced
+// again before it retires, by trav_step: every decision where the reference takes it, as rt_trace_rays.  That takes two
+// surfaces within 1e-6 of each other, the farther tested later: about every other ray through a shared edge or vertex
+// (tests/test_gpu_prim_edges.py), hardly any ray of a frame.
+//
 // ANY (occlusion): a lane stops after the first round in which it accepted a hit.  The any-hit traversal is a prefix
 // of the closest traversal of the same instance, so occluded == (the closest query finds a hit).
 
@@ -53,6 +66,8 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
 
     bool has = false;                  // lane owns a ray
     uint32_t idx = 0;                  // its index (< q.n whenever has)
+    float seen = 0.0f;                 // its tmax after the last round
+    bool grew = false;                 // a leaf phase raised it: the ray is traced again in the reference's order
     uint32_t pool_next = 0, pool_end = 0;     // wave-uniform: the claimed chunk's unassigned rays
     bool exhausted = false;                   // wave-uniform
     const uint32_t chunks = (q.n >> 6) + ((q.n & 63u) ? 1u : 0u);     // <= 2^26
@@ -87,6 +102,8 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
                 const f3 o = mk(r[0], r[1], r[2]);
                 const f3 d = mk(r[3], r[4], r[5]);
                 const float tmax = q.tmax ? q.tmax[idx] : __builtin_huge_valf();
+                seen = tmax;
+                grew = false;
                 if (tmax > TMIN) {
                     trav_init<XBOX(WIDE)>(T, root, o, d, tmax);
                 } else {                                              // empty range (NaN included): a miss
@@ -106,6 +123,10 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
                 if ((uint32_t)__popcll(want) >= QUERY_THRESHOLD) break;
             }
             spec_round<false, WIDE>(T, sc, spill, cnt, pc, steps, false, 0u);
+            if (!ANY) {
+                grew = grew || T.tmax > seen;
+                seen = T.tmax;
+            }
             if (ANY && T.tracing && T.found) {    // occlusion: the first accepted hit ends the ray
                 T.tracing = false;
                 T.cur = REF_NONE;
@@ -114,6 +135,11 @@ void ray_query_kernel(SceneGPU sc, RayQueryGPU q) {
             }
         }
         // ---- retire the lanes whose ray finished
+        if (!ANY && has && !T.tracing && grew) {      // (grew: the range was not empty, the ray was traversed)
+            const f3 o = T.wr.o, d = T.wr.d;
+            trav_init<XD_ALL>(T, *sc.tlas_root, o, d, q.tmax ? q.tmax[idx] : __builtin_huge_valf());
+            while (T.tracing) trav_step<false, XD_ALL>(T, sc, spill, cnt);
+        }
         if (has && !T.tracing) {
             if (ANY) {
                 q.occluded[idx] = T.found ? 1 : 0;
