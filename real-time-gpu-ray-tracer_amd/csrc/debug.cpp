@@ -51,7 +51,7 @@ rt_status gpu_blas_pairs(const rt_scene *s, size_t &count) {
     if (s->build_mode != RT_BUILD_LBVH || !s->blas_builder) return RT_OK;
     uint32_t n = 0;
     HIP_TRY(hipMemcpy(&n, s->gpu_counts.p, sizeof n, hipMemcpyDeviceToHost));
-    count = std::min<size_t>(n, s->blas_pairs.n);
+    count = std::min<size_t>(n, s->cur.pairs.n);
     return RT_OK;
 }
 
@@ -148,11 +148,11 @@ rt_status rt_scene_debug_read(rt_scene *s, const char *name, void *dst, size_t c
         if (!s->built || !s->gpu_tlas()) return fail(RT_ERR_UNSUPPORTED, "raw BLAS records are exported for RT_BUILD_LBVH only");
         HIP_TRY(hipSetDevice(s->device));
         RT_TRY(drain(s));
-        const void *from = k == "blas_pairs" ? (const void *)s->blas_pairs.p
-                                             : (k == "blas_quads" ? (const void *)s->blas_quads.p : (const void *)s->blas_roots.p);
+        const void *from = k == "blas_pairs" ? (const void *)s->cur.pairs.p
+                                             : (k == "blas_quads" ? (const void *)s->cur.quads.p : (const void *)s->cur.roots.p);
         size_t pair_count = 0;
         RT_TRY(gpu_blas_pairs(s, pair_count));
-        *bytes = k == "blas_roots" ? s->blas_roots.n * sizeof(TreeRoot)
+        *bytes = k == "blas_roots" ? s->cur.roots.n * sizeof(TreeRoot)
                                    : pair_count * (k == "blas_pairs" ? sizeof(NodePair) : sizeof(NodeQuad));
         if (capacity && *bytes) HIP_TRY(hipMemcpy(dst, from, std::min(capacity, *bytes), hipMemcpyDeviceToHost));
         return RT_OK;
@@ -162,12 +162,12 @@ rt_status rt_scene_debug_read(rt_scene *s, const char *name, void *dst, size_t c
         HIP_TRY(hipSetDevice(s->device));
         RT_TRY(drain(s));
         const bool raw = s->raw_shading();             // the index rides in TriHot::pad0 (option "cold_records" 0)
-        const size_t n = s->tri_hot.n;
+        const size_t n = s->cur.tri_hot.n;
         *bytes = n * sizeof(uint32_t);
         if (capacity && n) {
             const size_t m = std::min(capacity / sizeof(uint32_t), n);
-            const uint8_t *src0 = raw ? reinterpret_cast<const uint8_t *>(s->tri_hot.p) + offsetof(TriHot, pad0)
-                                      : reinterpret_cast<const uint8_t *>(s->tri_cold.p) + offsetof(TriCold, orig_index);
+            const uint8_t *src0 = raw ? reinterpret_cast<const uint8_t *>(s->cur.tri_hot.p) + offsetof(TriHot, pad0)
+                                      : reinterpret_cast<const uint8_t *>(s->cur.tri_cold.p) + offsetof(TriCold, orig_index);
             HIP_TRY(hipMemcpy2D(dst, sizeof(uint32_t), src0, raw ? sizeof(TriHot) : sizeof(TriCold), sizeof(uint32_t), m,
                                 hipMemcpyDeviceToHost));
         }
@@ -202,13 +202,13 @@ rt_status rt_scene_export_blas(const rt_scene *s, uint32_t b, float *boxes, uint
             return fail(RT_ERR_STATE, "this BLAS is not built: its instance group is one BLAS (option \"group\")");
         size_t pair_count = 0;
         RT_TRY(gpu_blas_pairs(s, pair_count));
-        HIP_TRY(read_back(pairs, s->blas_pairs.p, pair_count));
-        HIP_TRY(read_back(roots, s->blas_roots.p, s->blas_roots.n));
+        HIP_TRY(read_back(pairs, s->cur.pairs.p, pair_count));
+        HIP_TRY(read_back(roots, s->cur.roots.p, s->cur.roots.n));
         const uint32_t type = s->blas[b].type;
         std::vector<uint32_t> orig;
         if (type == RT_PRIM_TRIANGLE && s->raw_shading()) {
             std::vector<TriHot> h;
-            HIP_TRY(read_back(h, s->tri_hot.p, s->tri_hot.n));
+            HIP_TRY(read_back(h, s->cur.tri_hot.p, s->cur.tri_hot.n));
             for (const TriHot &x : h) {
                 uint32_t v;
                 std::memcpy(&v, &x.pad0, sizeof v);
@@ -216,12 +216,12 @@ rt_status rt_scene_export_blas(const rt_scene *s, uint32_t b, float *boxes, uint
             }
         } else if (type == RT_PRIM_TRIANGLE) {
             std::vector<TriCold> c;
-            HIP_TRY(read_back(c, s->tri_cold.p, s->tri_cold.n));
+            HIP_TRY(read_back(c, s->cur.tri_cold.p, s->cur.tri_cold.n));
             for (const TriCold &x : c) orig.push_back(x.orig_index);
         } else {
             std::vector<PrimCold> c;
-            HIP_TRY(read_back(c, type == RT_PRIM_SPHERE ? s->sph_cold.p : s->quad_cold.p,
-                              type == RT_PRIM_SPHERE ? s->sph_cold.n : s->quad_cold.n));
+            HIP_TRY(read_back(c, type == RT_PRIM_SPHERE ? s->cur.sph_cold.p : s->cur.quad_cold.p,
+                              type == RT_PRIM_SPHERE ? s->cur.sph_cold.n : s->cur.quad_cold.n));
             for (const PrimCold &x : c) orig.push_back(x.orig_index);
         }
         gpu_tree = tree_from_pairs(roots[s->seg_of_blas[b]], pairs, 0, orig);

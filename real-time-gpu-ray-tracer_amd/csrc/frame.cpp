@@ -103,7 +103,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
             }
             in.box.store(d.p.box);
             d.p.pad[0] = record_inactive(s, i) ? 1.0f : 0.0f;
-            d.p.pad[1] = !s->dev_bounded.empty() && s->dev_bounded[i] ? 1.0f : 0.0f;   // RT_TRI_UPDATE_BOUNDS
+            d.p.pad[1] = dev_bounded_rec(s, i) ? 1.0f : 0.0f;   // RT_TRI_UPDATE_BOUNDS
         }
         uint8_t *fd = s->frame_dev[b];
         uint32_t live = 0;                              // records in this frame's TLAS
@@ -120,7 +120,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
             s->blas_build_seq++;
         }
         // Every frame whose records / TLAS / trace run off the scene stream waits for the last BLAS build once per
-        // stream, not only the frame that enqueued it: a build swaps blas_roots / the primitive records to the set
+        // stream, not only the frame that enqueued it: a build swaps cur (the roots, the primitive records) to the set
         // being written ("blas_double") or rewrites them in place, and a later frame on another lane stream that
         // builds nothing would otherwise read them mid-build (rt_scene_update_triangles once, a group break)
         if (cs != s->stream && s->blas_build_seq != 0) RT_TRY(wait_blas_built(s, cs));
@@ -132,7 +132,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
                                        s->inst_params.p + (size_t)b * n, n,
                                        reinterpret_cast<InstHot *>(fd + s->off_hot), reinterpret_cast<InstCold *>(fd + s->off_cold),
                                        reinterpret_cast<float *>(fd + s->off_tbox), reinterpret_cast<float4 *>(fd + s->off_tcent),
-                                       s->inst_blas.p, s->blas_roots.p, s->blas_wide_refs.p, s->ib_cent.p, /*inf_inactive=*/!small, cs));
+                                       s->inst_blas.p, s->cur.roots.p, s->blas_wide_refs.p, s->ib_cent.p, /*inf_inactive=*/!small, cs));
         s->chain_stream[b] = cs;
         if (small) {
             // one workgroup: the LBVH TLAS over the live records, quads, slots, slot-ordered records (lbvh_tlas_small.hpp)
@@ -254,17 +254,17 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
 SceneGPU scene_gpu(const rt_scene *s) {
     SceneGPU g{};
     const int b = s->active;
-    g.blas_pairs = s->blas_pairs.p;
+    g.blas_pairs = s->cur.pairs.p;
     g.tlas_pairs = reinterpret_cast<const NodePair *>(s->frame_dev[b] + s->off_pairs);
     g.tlas_root = reinterpret_cast<const TreeRoot *>(s->frame_dev[b] + s->off_root);
     g.tlas_root_wide = reinterpret_cast<const TreeRoot *>(s->frame_dev[b] + s->off_root_wide);
     g.tlas_quads = reinterpret_cast<const NodeQuad *>(s->frame_dev[b] + s->off_quads);
-    g.blas_quads = s->blas_quads.p;
+    g.blas_quads = s->cur.quads.p;
     // quad trees (GPU-built: from collapse_wide): 1 = host SAH BLASes collapsed greedily, visited by entry t; 2 = two
     // binary levels per quad visited in the reference's order (GPU-built trees); 3 = the same with every box decision
     // inside the FAST slab's error margin re-taken with the reference's slab (the reference's own trees; GPU-built
     // trees with option "exact_decisions")
-    g.wide = s->wide && s->blas_quads.p != nullptr
+    g.wide = s->wide && s->cur.quads.p != nullptr
                  ? (s->quad_halves() ? ((s->build_mode == RT_BUILD_COMPAT_MEDIAN || s->exact_decisions) ? 3u : 2u) : 1u)
                  : 0u;
     g.tlas_slots = reinterpret_cast<const uint32_t *>(s->frame_dev[b] + s->off_slots);
@@ -272,10 +272,10 @@ SceneGPU scene_gpu(const rt_scene *s) {
     g.inst_hot = reinterpret_cast<const InstHot *>(s->frame_dev[b] + (gpu_slots ? s->off_hot_s : s->off_hot));
     g.inst_cold = reinterpret_cast<const InstCold *>(s->frame_dev[b] + (gpu_slots ? s->off_cold_s : s->off_cold));
     g.inst_by_slot = s->block_by_slot[b] ? 1u : 0u;   // how frame block b's instance records were staged
-    g.tri_hot = s->tri_hot.p; g.tri_cold = s->raw_shading() ? nullptr : s->tri_cold.p;
+    g.tri_hot = s->cur.tri_hot.p; g.tri_cold = s->raw_shading() ? nullptr : s->cur.tri_cold.p;
     g.raw_tris = s->raw_shading() ? s->raw_tris.p : nullptr;
-    g.sph_hot = s->sph_hot.p; g.sph_cold = s->sph_cold.p;
-    g.quad_hot = s->quad_hot.p; g.quad_cold = s->quad_cold.p;
+    g.sph_hot = s->cur.sph_hot.p; g.sph_cold = s->cur.sph_cold.p;
+    g.quad_hot = s->cur.quad_hot.p; g.quad_cold = s->cur.quad_cold.p;
     g.materials = s->materials.p;
     g.instance_count = s->frame_items[b];   // records the frame's TLAS holds (GPU-built, small path: the live ones)
     g.rough_count = (uint32_t)s->roughs.size();
@@ -292,7 +292,7 @@ SceneGPU scene_gpu(const rt_scene *s) {
             if (nq * LDS_QUAD_F4 + n * LDS_INST_F4 <= LDS_SCENE_F4) g.lds_insts = n;
         }
         uint32_t at = s->lds_scene >= 2 ? g.lds_quads * LDS_QUAD_F4 + g.lds_insts * LDS_INST_F4 : LDS_SCENE_F4;
-        const uint32_t ns = (uint32_t)s->sph_hot.n, nqd = (uint32_t)s->quad_hot.n;
+        const uint32_t ns = (uint32_t)s->cur.sph_hot.n, nqd = (uint32_t)s->cur.quad_hot.n;
         if (ns > 0 && at + 2 * ns <= LDS_SCENE_F4) { g.lds_sph_hot = at; g.lds_sph_cold = at + ns; at += 2 * ns; }
         if (nqd > 0 && at + (LDS_QPRIM_F4 + 1) * nqd <= LDS_SCENE_F4) {
             g.lds_q_hot = at; g.lds_q_cold = at + LDS_QPRIM_F4 * nqd; at += (LDS_QPRIM_F4 + 1) * nqd;

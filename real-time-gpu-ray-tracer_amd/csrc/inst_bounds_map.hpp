@@ -3,7 +3,7 @@
 // the header is plain C++ without HIP types.
 //
 // An instance's local centroid is (float)(S / count), S the double-precision sum of its `count` triangle centroids
-// (build.cpp bounds_from_prims).  The device forms S in a fixed shape that depends on `count` alone:
+// (build.cpp bounds_from_prims, update.cpp host_bounds).  The device forms S in a fixed shape that depends on `count` alone:
 //   chunk   the instance's triangles are cut into chunks of IB_CHUNK; chunk c holds triangles [c IB_CHUNK, ...).  One
 //           workgroup of IB_WAVES waves of IB_WAVE lanes sums a chunk in IB_ROUNDS rounds: in round r, lane l of wave w
 //           holds triangle ib_tri(c, r, w, l) (a triangle past `count` counts as +0.0).

@@ -379,7 +379,7 @@ rt_status rt_render(rt_scene *s, uint64_t frame, const rt_render_opts *opts, uin
     }
     s->r_used[s->active] = s->r_done = s->r_lane[q] = done;
     if (copied_block >= 0) s->r_copied[copied_block] = s->r_staged[copied_stage] = done;
-    if (s->ev_blas_lane[q]) HIP_TRY(hipEventRecord(s->ev_blas_lane[q], stream));   // "blas_double": this set's reader
+    if (s->cur.ev_lane[q]) HIP_TRY(hipEventRecord(s->cur.ev_lane[q], stream));   // "blas_double": this set's reader
     if (order_null && !lib_lane) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
     if (o.flags & RT_RENDER_NO_SYNC) {
         if (stats) { std::memset(stats, 0, sizeof *stats); stats->update_ms = update_ms; stats->update_wait_ms = s->update_wait_ms; }
@@ -486,7 +486,7 @@ rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
     // purposes often share one event (a frame's single completion event): each is waited on once.
     const int bl = s->last_lane;
     hipEvent_t prev_query = s->ev_query[(slot + rt_scene::NQUERY - 1) % rt_scene::NQUERY];
-    hipEvent_t deps[] = {done, prev_query, s->r_copied[b], s->r_used[b], s->r_done, s->ev_blas_lane[bl]};
+    hipEvent_t deps[] = {done, prev_query, s->r_copied[b], s->r_used[b], s->r_done, s->cur.ev_lane[bl]};
     for (size_t i = 0; i < sizeof deps / sizeof deps[0]; i++) {
         bool dup = !deps[i];
         for (size_t j = 0; j < i && !dup; j++) dup = deps[j] == deps[i];
@@ -508,7 +508,7 @@ rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
     s->query_next = (slot + 1) % rt_scene::NQUERY;
     s->query_live = true;
     s->r_used[b] = s->r_done = done;           // later uploads into block b, later BLAS rebuilds, rt_synchronize
-    if (s->ev_blas_lane[bl]) HIP_TRY(hipEventRecord(s->ev_blas_lane[bl], st));   // "blas_double": this set's reader
+    if (s->cur.ev_lane[bl]) HIP_TRY(hipEventRecord(s->cur.ev_lane[bl], st));   // "blas_double": this set's reader
     if (!qy->stream) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
     if (qy->flags & RT_QUERY_NO_SYNC) return RT_OK;
     return wait_event(s, done);

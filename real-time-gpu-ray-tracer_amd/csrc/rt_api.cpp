@@ -12,7 +12,9 @@
 //   launch.hpp      the kernel launchers and the EXACT / FAST / fast_math table
 //   scene_sync.cpp  ~rt_scene, drain and the other waits, order_after_null_stream
 //   frame.cpp       frame_update (the host half of a frame), scene_gpu
-//   build.cpp       rt_scene_build, the GPU BLAS builds, rt_scene_update_triangles / _triangles_device / _instances
+//   build.cpp       rt_scene_build and its steps; the primitives' bounds and material slots
+//   blas_gpu.cpp    the GPU BLAS builds of RT_BUILD_LBVH and their segments
+//   update.cpp      rt_scene_update_triangles / _triangles_device / _instances, the device-bounds state
 //   render.cpp      rt_render with auto_lanes and order_null, rt_assemble_tiles, rt_trace_rays, rt_query_rays, rt_box_test
 //   scene_comm.cpp  the RCCL attach / detach / abort path and a frame's gather
 //   debug.cpp       rt_scene_debug_read, rt_scene_export_blas / _tlas
@@ -313,18 +315,12 @@ rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *info) {
         info->tlas_node_pairs = np;
         info->tlas_height = root.height;
     }
-    info->device_bytes = s->blas_pairs.n * sizeof(NodePair) + s->tri_hot.n * sizeof(TriHot) + s->tri_cold.n * sizeof(TriCold) +
-                         s->sph_hot.n * sizeof(SphereHot) + s->sph_cold.n * sizeof(PrimCold) +
-                         s->quad_hot.n * sizeof(QuadHot) + s->quad_cold.n * sizeof(PrimCold) +
+    // the live set's roots have never been counted (the spares' are); nor inst_blas, gpu_counts, the ib_* tables
+    info->device_bytes = s->cur.bytes() - s->cur.roots.bytes() +
                          s->materials.n * sizeof(float) + 2 * s->frame_block + s->out_rgba.n + s->out_rgb.n * sizeof(float) +
                          s->raw_tris.n * sizeof(rt_triangle) + s->raw_sph.n * sizeof(rt_sphere) +
-                         s->raw_quad.n * sizeof(rt_parallelogram) + s->blas_quads.n * sizeof(NodeQuad) +
-                         s->raw_verts.n * sizeof(float);
-    for (const auto &sp : s->spare)      // the spare BLAS sets of per-frame rebuilds ("blas_sets")
-        info->device_bytes += sp.pairs.n * sizeof(NodePair) + sp.quads.n * sizeof(NodeQuad) + sp.roots.n * sizeof(TreeRoot) +
-                              sp.tri_hot.n * sizeof(TriHot) + sp.tri_cold.n * sizeof(TriCold) +
-                              sp.sph_hot.n * sizeof(SphereHot) + sp.sph_cold.n * sizeof(PrimCold) +
-                              sp.quad_hot.n * sizeof(QuadHot) + sp.quad_cold.n * sizeof(PrimCold);
+                         s->raw_quad.n * sizeof(rt_parallelogram) + s->raw_verts.n * sizeof(float);
+    for (const auto &sp : s->spare) info->device_bytes += sp.bytes();   // per-frame rebuilds ("blas_sets")
     if (s->blas_builder) info->device_bytes += s->blas_builder->workspace_bytes();   // incl. the staged TriHot records
     if (s->tlas_builder) info->device_bytes += s->tlas_builder->workspace_bytes();
     info->width = s->width; info->height = s->height;

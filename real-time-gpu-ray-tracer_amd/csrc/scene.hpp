@@ -1,6 +1,7 @@
 // scene.hpp — the scene's state (struct rt_scene) and the internal interface between the host files: the error and
-// wait discipline (scene_sync.cpp), the host half of a frame (frame.cpp), the acceleration-structure builds
-// (build.cpp), the RCCL path (scene_comm.cpp); render.cpp, debug.cpp and rt_api.cpp only call into them.
+// wait discipline (scene_sync.cpp), the host half of a frame (frame.cpp), the acceleration-structure builds (build.cpp,
+// blas_gpu.cpp), the geometry updates (update.cpp), the RCCL path (scene_comm.cpp); render.cpp, debug.cpp and
+// rt_api.cpp only call into them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -139,9 +140,43 @@ struct rt_scene {
     bool built = false;
     uint64_t frame = 0;
 
-    // HBM: static scene data
-    DevBuf<NodePair> blas_pairs;
-    DevBuf<NodeQuad> blas_quads;    // option "wide"
+    // HBM: static scene data.  A BLAS set: the node pairs, quads and roots of every BLAS and the leaf-ordered primitive
+    // records, with each lane's last trace that read them (RT_BUILD_LBVH rebuilds, below).  Every DevBuf is named in
+    // each_buf(), which release(), bytes() and alloc_like() walk.
+    struct BlasSet {
+        DevBuf<NodePair> pairs;
+        DevBuf<NodeQuad> quads;         // option "wide"
+        DevBuf<TreeRoot> roots;         // per segment the builder holds (seg_of_blas)
+        DevBuf<TriHot> tri_hot; DevBuf<TriCold> tri_cold; DevBuf<SphereHot> sph_hot; DevBuf<PrimCold> sph_cold;
+        DevBuf<QuadHot> quad_hot; DevBuf<PrimCold> quad_cold;
+        hipEvent_t ev_lane[NBLOCK] = {};   // one per lane: its last trace of this set
+        template <typename Self, typename F>
+        static void each_buf(Self &b, F f) {
+            f(b.pairs); f(b.quads); f(b.roots); f(b.tri_hot); f(b.tri_cold); f(b.sph_hot); f(b.sph_cold); f(b.quad_hot); f(b.quad_cold);
+        }
+        void release() { each_buf(*this, [](auto &b) { b.release(); }); }
+        size_t bytes() const {
+            size_t n = 0;
+            each_buf(*this, [&](const auto &b) { n += b.bytes(); });
+            return n;
+        }
+        // every buffer allocated anew for o's element counts (DevBuf::alloc: one element where o holds none, as a
+        // released tri_cold)
+        hipError_t alloc_like(const BlasSet &o) {
+            std::vector<size_t> n;
+            each_buf(o, [&](const auto &b) { n.push_back(b.n); });
+            hipError_t e = hipSuccess;
+            size_t k = 0;
+            each_buf(*this, [&](auto &b) { if (e == hipSuccess) e = b.alloc(n[k++]); });
+            return e;
+        }
+        // what a spare set is re-sized by: the counts a change of the segments or of the scene's primitives moves
+        bool sized_as(const BlasSet &o) const {
+            return pairs.n == o.pairs.n && tri_hot.n == o.tri_hot.n && sph_hot.n == o.sph_hot.n && quad_hot.n == o.quad_hot.n &&
+                   roots.n == o.roots.n;
+        }
+    };
+    BlasSet cur;                    // the set the traces read
     bool wide = true;               // FAST persistent kernel traverses the quad trees (host-built modes)
     bool exact_decisions = false;   // option "exact_decisions": GPU-built trees take the exact-decision traversal (mode 3)
     uint32_t lds_scene = 2;         // quad-tree kernel: 1 = TLAS quads (+ instance hot records) in LDS when they
@@ -164,12 +199,6 @@ struct rt_scene {
     int cold_records = -1;
     bool cold_eff = false;          // the build's choice (rt_scene_build)
     bool raw_shading() const { return build_mode == RT_BUILD_LBVH && !cold_eff; }
-    DevBuf<TriHot> tri_hot;
-    DevBuf<TriCold> tri_cold;
-    DevBuf<SphereHot> sph_hot;
-    DevBuf<PrimCold> sph_cold;
-    DevBuf<QuadHot> quad_hot;
-    DevBuf<PrimCold> quad_cold;
     DevBuf<float> materials;
     uint64_t blas_pair_count = 0, blas_leaf_count = 0;
 
@@ -342,7 +371,7 @@ struct rt_scene {
     hipEvent_t ev_raw_staged = nullptr;            // the last staged copy finished (raw_stage reusable)
     // rt_scene_update_triangles_device: its kernel's completion (the caller's stream waits on it; the scene stream
     // orders everything else), and whether `tris` still mirrors raw_tris: the kernel's vertices and normals never
-    // reach the host, so whoever reads the mirror's geometry first calls refresh_tris_mirror (build.cpp)
+    // reach the host, so whoever reads the mirror's geometry first calls refresh_tris_mirror (update.cpp)
     hipEvent_t ev_tri_update = nullptr;
     bool tris_host_stale = false;
     // RT_TRI_UPDATE_BOUNDS (inst_bounds.hip): per record (instances, then groups) whether the device holds its local
@@ -351,7 +380,8 @@ struct rt_scene {
     // centroid of such a record are stale.  The static tables of the build (InstBoundsGPU, launch.hpp); ib_cent holds
     // every record's local centroid, the host-bounded ones' uploaded at the build and whenever the host changes one
     // that a group's mean reads (refresh_dev_centroids, through the pinned ib_cent_stage, slot = record)
-    std::vector<uint8_t> dev_bounded;
+    std::vector<uint8_t> dev_bounded;   // empty outside RT_BUILD_LBVH (dev_bounded_rec)
+    static constexpr uint32_t NONE = 0xFFFFFFFFu;   // ib_entry_of, seg_of_blas: no entry
     std::vector<uint32_t> ib_entry_of;  // instance -> entry of ib_table (NONE: not a triangle instance)
     DevBuf<InstBoundsEntry> ib_table;
     DevBuf<uint32_t> ib_chunk_inst, ib_multi, ib_members;
@@ -361,7 +391,6 @@ struct rt_scene {
     float4 *ib_cent_stage = nullptr;
     DevBuf<rt_sphere> raw_sph;
     DevBuf<rt_parallelogram> raw_quad;
-    DevBuf<TreeRoot> blas_roots;        // per segment the builder holds (seg_of_blas)
     DevBuf<uint32_t> inst_blas;         // instance record (instances, then groups) -> segment
     // RT_BUILD_LBVH + option "group": every unique BLAS's segment (index = BLAS index; the groups' merged BLASes
     // follow the own ones), BLAS -> segment the builder currently holds (NONE: not built), and per group whether
@@ -375,24 +404,13 @@ struct rt_scene {
     bool blas_dirty = false;            // rt_scene_update_triangles since the last BLAS build
     // RT_BUILD_LBVH rebuilds (option "blas_double", default on): a rebuild writes a spare BLAS set and swaps it
     // in, so frame k+1's rebuild runs while frame k's trace still reads the other set (C5: the rebuild no
-    // longer waits for every lane's trace).  ev_blas_lane[q]: lane q's last trace of the current set.
+    // longer waits for every lane's trace).  cur.ev_lane[q]: lane q's last trace of the current set.
     // Option "blas_sets" = 3 (default; 2 = one spare): two spare sets in rotation, so frame k+1's rebuild waits only
     // for frame k-2's trace and three traces stay in flight beside it (spare[0] = the set read longest ago, the next
     // one written; C5 with the rebuild 11.18 -> 10.85 ms/frame, profiles/r04/c5_rebuild/).
-    struct BlasSet {
-        DevBuf<NodePair> pairs; DevBuf<NodeQuad> quads; DevBuf<TreeRoot> roots;
-        DevBuf<TriHot> tri_hot; DevBuf<TriCold> tri_cold; DevBuf<SphereHot> sph_hot; DevBuf<PrimCold> sph_cold;
-        DevBuf<QuadHot> quad_hot; DevBuf<PrimCold> quad_cold;
-        hipEvent_t ev_lane[NLANE] = {};
-        void release() {
-            pairs.release(); quads.release(); roots.release(); tri_hot.release(); tri_cold.release();
-            sph_hot.release(); sph_cold.release(); quad_hot.release(); quad_cold.release();
-        }
-    };
     static constexpr uint32_t MAX_BLAS_SETS = 8;
     BlasSet spare[MAX_BLAS_SETS - 1];   // spare[0]: the set read longest ago (written next) .. spare[sets - 2]: the newest
     uint32_t blas_sets = 3;
-    hipEvent_t ev_blas_lane[NLANE] = {};
     bool blas_double = true;
     uint64_t blas_builds = 0;
     hipEvent_t ev_render_done = nullptr;   // last trace launch finished (BLAS rebuilds wait on it)
@@ -472,14 +490,30 @@ bool record_inactive(const rt_scene *s, size_t i);
 const InstState &record_state(const rt_scene *s, size_t i);
 bool group_intact(const rt_scene *s, size_t g);
 
-// build.cpp
+// build.cpp: rt_scene_build; the primitives' bounds and materials as every builder reads them
 size_t prim_len(const rt_scene *s, uint32_t type);
+hm::Box prim_box(const rt_scene *s, uint32_t type, uint32_t i);
+hm::V3 prim_centroid(const rt_scene *s, uint32_t type, uint32_t i);
+void bounds_from_prims(const rt_scene *s, InstState &in);
+void bounds_from_desc(const rt_instance_desc &d, InstState &in);
+void group_bounds(const rt_scene *s, InstGroup &G);
+uint32_t material_slot(const rt_scene *s, uint32_t type, uint32_t index, bool &ok);
+rt_status check_materials(bool ok, const char *what = "primitive");   // `ok` as material_slot left it
+template <typename T>
+rt_status check_materials(const rt_scene *s, const T *prims, size_t count, const char *what = "primitive") {
+    bool ok = true;
+    for (size_t k = 0; k < count; k++) material_slot(s, prims[k].material_type, prims[k].material_index, ok);
+    return check_materials(ok, what);
+}
+// blas_gpu.cpp: the RT_BUILD_LBVH BLASes, built on the GPU
 rt_status lbvh_segments(rt_scene *s);
 rt_status lbvh_sync_groups(rt_scene *s);
 rt_status gpu_build_blas(rt_scene *s);
 rt_status gpu_setup_blas(rt_scene *s, const uint32_t *slot_count);
+// update.cpp: the geometry updates between frames
 rt_status refresh_tris_mirror(rt_scene *s);
 rt_status setup_inst_bounds(rt_scene *s);
+inline bool dev_bounded_rec(const rt_scene *s, size_t record) { return !s->dev_bounded.empty() && s->dev_bounded[record]; }
 
 // scene_comm.cpp: a multi-GPU frame's gather to rank 0 and its assembly there, on the trace's stream
 rt_status comm_gather(rt_scene *s, int q, uint8_t *frame_out, hipStream_t stream);

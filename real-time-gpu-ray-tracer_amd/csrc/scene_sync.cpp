@@ -25,23 +25,23 @@ rt_scene::~rt_scene() {
     for (hipEvent_t e : ev_query)            // ray queries still running on caller streams
         if (e) (void)hipEventSynchronize(e);
     release_comm();
-    blas_pairs.release(); blas_quads.release(); tri_hot.release(); tri_cold.release(); sph_hot.release(); sph_cold.release();
-    quad_hot.release(); quad_cold.release(); materials.release(); out_rgba.release(); out_rgb.release();
+    materials.release(); out_rgba.release(); out_rgb.release();
     timeline.release(); costmap.release();
     for (int q = 0; q < NLANE; q++) { unit_cost[q].release(); unit_order[q].release(); }
     delete blas_builder; delete tlas_builder;
-    raw_tris.release(); raw_verts.release(); raw_sph.release(); raw_quad.release(); blas_roots.release(); inst_blas.release();
+    raw_tris.release(); raw_verts.release(); raw_sph.release(); raw_quad.release(); inst_blas.release();
     blas_wide_refs.release();
     gpu_counts.release(); inst_params.release();
     ib_table.release(); ib_chunk_inst.release(); ib_multi.release(); ib_members.release(); ib_groups.release();
     ib_partials.release(); ib_cent.release();
     if (ib_cent_stage) (void)hipHostFree(ib_cent_stage);
-    for (BlasSet &sp : spare) sp.release();
-    for (int q = 0; q < NLANE; q++) {
-        if (ev_blas_lane[q]) (void)hipEventDestroy(ev_blas_lane[q]);
-        for (BlasSet &sp : spare)
-            if (sp.ev_lane[q]) (void)hipEventDestroy(sp.ev_lane[q]);
-    }
+    const auto drop = [](BlasSet &b) {             // every BLAS set, live or spare: its buffers and lane events
+        b.release();
+        for (hipEvent_t e : b.ev_lane)
+            if (e) (void)hipEventDestroy(e);
+    };
+    drop(cur);
+    for (BlasSet &sp : spare) drop(sp);
     if (ev_render_done) (void)hipEventDestroy(ev_render_done);
     if (ev_caller) (void)hipEventDestroy(ev_caller);
     if (ev_blas_built) (void)hipEventDestroy(ev_blas_built);

@@ -38,7 +38,7 @@ int main(int argc, char **argv) {
     std::vector<InstBoundsEntry> table;
     std::vector<uint32_t> chunk_inst;
     uint64_t at = first_tri;
-    for (int k = 3; k < argc; k++) {                                   // as setup_inst_bounds (build.cpp)
+    for (int k = 3; k < argc; k++) {                                   // as setup_inst_bounds (update.cpp)
         const uint32_t count = (uint32_t)std::strtoul(argv[k], nullptr, 10);
         if (count == 0 || (at + count) * 9 > all.size()) return 2;
         table.push_back(InstBoundsEntry{(uint32_t)at, count, (uint32_t)chunk_inst.size(), (uint32_t)table.size()});

@@ -1,5 +1,5 @@
 """RT_TRI_UPDATE_BOUNDS on the CPU: a numpy restatement of the centroid reduction's shape (csrc/inst_bounds_map.hpp), the
-host path's rule it must reproduce (build.cpp bounds_from_prims), and the scenes of tests/test_gpu_update_device_bounds.py,
+host path's rule it must reproduce (build.cpp bounds_from_prims, update.cpp host_bounds), and the scenes of tests/test_gpu_update_device_bounds.py,
 so that tests/test_inst_bounds_ref.py can check without a GPU what those tests rest on.
 
 Scenes.  particles(P, T) is scenes.synth_particles cut to the first T triangles of each particle (the generator makes

@@ -518,6 +518,29 @@ def test_cold_records_auto_same_frames(gpu_lib, rebuild):
         assert dev[1] > dev[0], dev
 
 
+@pytest.mark.parametrize("group", [0, 1])
+def test_every_spare_blas_set_costs_the_same(gpu_lib, group):
+    """A per-frame rebuild in place ("blas_double" 0), with one spare BLAS set ("blas_sets" 2) and with two (3): after
+    four frames every spare is in use, each is a copy of the live set's buffers, so each adds the same bytes to
+    device_bytes (a buffer missing from, or counted twice in, one of the walks over a set's buffers would break the
+    equality), and the three runs render the same bytes."""
+    s = scenes.demo_with_particles(6)
+    dev, frames = [], []
+    for opts in ({"blas_double": 0}, {"blas_sets": 2}, {"blas_sets": 3}):
+        r = Renderer(s).set_option("group", group).set_option("rebuild", 1)
+        for k, v in opts.items():
+            r.set_option(k, v)
+        r.build_acceleration_structure(0, mode="lbvh").configure_camera(96, 64, ray_trace_depth=2)
+        frames.append([r.render(f)[0] for f in range(4)])
+        dev.append(r.info()["device_bytes"])
+        r.cleanup()
+    d0, d2, d3 = dev
+    assert d2 > d0 and d3 - d2 == d2 - d0, dev
+    for other in frames[1:]:
+        for a, b in zip(frames[0], other):
+            assert np.array_equal(a, b)
+
+
 def test_rebuild_stage_timing(gpu_lib):
     """Option "timeline" times the GPU BLAS rebuild's stages (bench.py's "rebuild" roofline block): after a timed
     rebuild rt_scene_debug_read("rebuild_stages") gives the forest's items, interior nodes, node pairs, items in

@@ -1,4 +1,4 @@
-"""rt_scene_update_triangles_device (csrc/tri_update.hip, build.cpp): triangle geometry handed over in device memory.
+"""rt_scene_update_triangles_device (csrc/tri_update.hip, update.cpp): triangle geometry handed over in device memory.
 
 Scenes are scenes.demo_with_particles(8): 8 192 particle triangles whose instances carry their own bounds, then the
 demo's own triangle at index 8 192, whose instance derives its bounds from it.  Frames are 256 x 144 at depth 2, as in

@@ -1,4 +1,4 @@
-"""RT_TRI_UPDATE_BOUNDS (csrc/inst_bounds.hip, instances.hip, build.cpp): a device triangle update that also derives the
+"""RT_TRI_UPDATE_BOUNDS (csrc/inst_bounds.hip, instances.hip, update.cpp): a device triangle update that also derives the
 bounds of the instances it overlaps on the device.
 
 Scenes are inst_bounds_ref.particles(P, T): scenes.synth_particles cut to T triangles per particle and translated so that
