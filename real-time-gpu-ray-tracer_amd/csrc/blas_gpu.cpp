@@ -90,8 +90,8 @@ rt_status gpu_build_blas(rt_scene *s) {
     } else {
         // in place: after every trace
         if (s->blas_builds && s->r_done) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_done, 0));
-        for (int q = 0; q < rt_scene::NLANE; q++)      // "overlap": the other lane's trace may still be running
-            if (s->blas_builds && s->r_lane[q]) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_lane[q], 0));
+        for (const Lane &l : s->ln)                    // "overlap": the other lane's trace may still be running
+            if (s->blas_builds && l.r_done) HIP_TRY(hipStreamWaitEvent(s->stream, l.r_done, 0));
     }
     // ray queries on caller streams; a frame on the lane may also have re-recorded a query's reader event
     RT_TRY(wait_queries(s, s->stream));
@@ -141,8 +141,6 @@ rt_status gpu_setup_blas(rt_scene *s, const uint32_t *slot_count) {
     for (rt_scene::BlasSet &sp : s->spare) sp.release();
     RT_TRY(lbvh_segments(s));
     RT_TRY(alloc_buf(s->gpu_counts, 2 + rt_scene::NLANE));
-    if (!s->ev_render_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_render_done, hipEventDisableTiming));
-    if (!s->r_done) s->r_done = s->ev_render_done;
     for (int q = 0; q < rt_scene::NLANE; q++) {       // "blas_double": every trace records its lane's event from now on
         if (!c.ev_lane[q]) HIP_TRY(hipEventCreateWithFlags(&c.ev_lane[q], hipEventDisableTiming));
         for (rt_scene::BlasSet &sp : s->spare)

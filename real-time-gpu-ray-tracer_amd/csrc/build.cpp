@@ -350,20 +350,9 @@ rt_status setup_gpu_tlas(rt_scene *s) {
 // The frame blocks and what every lane and launch needs: staging reset, events, counters, queue heads, query slots.
 // Everything that survives a rebuild is created once.
 rt_status setup_frame_resources(rt_scene *s) {
-    for (int i = 0; i < rt_scene::NSTAGE; i++) {
-        if (s->staging[i]) { (void)hipHostFree(s->staging[i]); s->staging[i] = nullptr; }   // frame_update allocates
-        s->staging_dev[i] = nullptr;
-        s->r_staged[i] = nullptr;
-    }
+    for (Stage &st : s->stg) st.release();         // frame_update allocates
     s->stage_next = 0;
-    for (int b = 0; b < rt_scene::NLANE; b++) {
-        if (s->frame_dev[b]) { (void)hipFree(s->frame_dev[b]); s->frame_dev[b] = nullptr; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->frame_dev[b]), s->frame_block));
-        if (!s->ev_copied[b]) HIP_TRY(hipEventCreateWithFlags(&s->ev_copied[b], hipEventDisableTiming));
-        if (!s->ev_used[b]) HIP_TRY(hipEventCreateWithFlags(&s->ev_used[b], hipEventDisableTiming));
-        if (!s->r_copied[b]) s->r_copied[b] = s->ev_copied[b];
-        if (!s->r_used[b]) s->r_used[b] = s->ev_used[b];
-    }
+    for (FrameBlock &b : s->blk) HIP_TRY(b.alloc(s->frame_block));
     for (uint32_t i = 0; i < rt_scene::RING; i++) {
         if (!s->ring_start[i]) HIP_TRY(hipEventCreate(&s->ring_start[i]));
         if (!s->ring_stop[i]) HIP_TRY(hipEventCreate(&s->ring_stop[i]));
@@ -373,14 +362,7 @@ rt_status setup_frame_resources(rt_scene *s) {
         HIP_TRY(hipMalloc(&s->counters, rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(s->counters, 0, rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long)));
     }
-    for (int q = 0; q < rt_scene::NLANE; q++) {
-        if (!s->queue[q]) {   // band heads, then (option "reorder") band item counts, one 128 B line each
-            HIP_TRY(hipMalloc(&s->queue[q], QUEUE_WORDS * sizeof(uint32_t)));
-            HIP_TRY(hipMemset(s->queue[q], 0, QUEUE_WORDS * sizeof(uint32_t)));
-        }
-        if (!s->ev_lane_done[q]) HIP_TRY(hipEventCreateWithFlags(&s->ev_lane_done[q], hipEventDisableTiming));
-        if (!s->r_lane[q]) s->r_lane[q] = s->ev_lane_done[q];
-    }
+    for (Lane &l : s->ln) HIP_TRY(l.create());
     {
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, s->device));
@@ -419,15 +401,13 @@ rt_status rt_scene_build(rt_scene *s, rt_build_mode mode, uint64_t seed) {
     s->inst.clear(); s->blas.clear();
     s->groups.clear(); s->group_of.clear();
     s->max_blas_height = 0;
-    for (bool &v : s->block_by_slot) v = false;    // a rebuild may change the mode: no block is slot-ordered yet
+    for (FrameBlock &b : s->blk) b.by_slot = false;   // a rebuild may change the mode: no block is slot-ordered yet
     BlasCursor at;
     RT_TRY(build_instances(s, at));
     RT_TRY(build_groups(s, at));
     // the scene stream (uploads, GPU BLAS builds) at normal priority: the highest measured neutral (round 3)
     if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->ev_render_done) HIP_TRY(hipEventCreateWithFlags(&s->ev_render_done, hipEventDisableTiming));
-    if (!s->r_done) s->r_done = s->ev_render_done;
-    for (bool &v : s->sched_valid) v = false;
+    s->forget_schedules();
     if (mode == RT_BUILD_LBVH) RT_TRY(gpu_setup_blas(s, at.slot));
     else RT_TRY(upload_host_blases(s, at));
     RT_TRY(upload_materials(s));

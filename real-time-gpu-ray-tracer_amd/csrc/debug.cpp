@@ -123,7 +123,7 @@ rt_status rt_scene_debug_read(rt_scene *s, const char *name, void *dst, size_t c
         const size_t n = s->inst.size();
         *bytes = n * 45 * sizeof(float);
         if (capacity) {
-            const uint8_t *fd = s->frame_dev[s->active];
+            const uint8_t *fd = s->blk[s->active].dev;
             std::vector<InstHot> hot;
             std::vector<InstCold> cold;
             std::vector<float> tbox, tcent;
@@ -173,10 +173,10 @@ rt_status rt_scene_debug_read(rt_scene *s, const char *name, void *dst, size_t c
         }
         return RT_OK;
     } else if (k == "unit_cost" || k == "unit_order") {
-        const int q = s->last_lane;
-        const size_t units = s->sched_sig[q][0];
-        src = k == "unit_cost" ? s->unit_cost[q].p + units : s->unit_order[q].p;
-        size = s->sched_valid[q] ? units * (k == "unit_cost" ? 1 : 4) * sizeof(uint32_t) : 0;
+        const Lane &l = s->ln[s->last_lane];
+        const size_t units = l.sig[0];
+        src = k == "unit_cost" ? l.unit_cost.p + units : l.unit_order.p;
+        size = l.valid ? units * (k == "unit_cost" ? 1 : 4) * sizeof(uint32_t) : 0;
     } else {
         return fail(RT_ERR_INVALID_ARGUMENT, "unknown debug buffer " + k);
     }
@@ -242,7 +242,7 @@ rt_status rt_scene_export_tlas(const rt_scene *s, float *boxes, uint32_t *ci, ui
     if (s->gpu_tlas()) {
         HIP_TRY(hipSetDevice(s->device));
         RT_TRY(wait_frame_block(const_cast<rt_scene *>(s)));   // the frame's TLAS may have been built on a lane stream
-        const uint8_t *fd = s->frame_dev[s->active];
+        const uint8_t *fd = s->blk[s->active].dev;
         TreeRoot root{};
         std::vector<NodePair> pairs;
         std::vector<uint32_t> slots;

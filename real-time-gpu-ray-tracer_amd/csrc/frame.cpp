@@ -51,14 +51,17 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
     const auto w0 = std::chrono::steady_clock::now();
     const int si = s->stage_next % s->stage_depth;      // this frame's staging buffer
     s->stage_next = (si + 1) % s->stage_depth;
-    if (s->r_staged[si]) RT_TRY(wait_event(s, s->r_staged[si]));   // no longer read by a pending copy
-    if (!s->staging[si]) {
+    Stage &stage = s->stg[si];
+    FrameBlock &blk = s->blk[b];
+    if (stage.r_staged) RT_TRY(wait_event(s, stage.r_staged));   // no longer read by a pending copy
+    if (!stage.host) {
         // every buffer of the cycle at once, on the first frame that needs one: a pinned allocation inside a run of
         // pipelined frames stalls the host's submission (one per frame for the first stage_depth frames)
         for (int i = 0; i < s->stage_depth; i++) {
-            if (s->staging[i]) continue;
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->staging[i]), s->frame_block, hipHostMallocDefault));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->staging_dev[i]), s->staging[i], 0));
+            Stage &n = s->stg[i];
+            if (n.host) continue;
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&n.host), s->frame_block, hipHostMallocDefault));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&n.dev), n.host, 0));
         }
     }
     s->update_wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
@@ -74,12 +77,12 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
                 else instance_update(s->inst[i], xs[i]);
             }
     }
-    uint8_t *st = s->staging[si];
+    uint8_t *st = stage.host;
     InstHot *hot = reinterpret_cast<InstHot *>(st + s->off_hot);
     InstCold *cold = reinterpret_cast<InstCold *>(st + s->off_cold);
     if (s->gpu_tlas()) {
         RT_TRY(lbvh_sync_groups(s));                  // option "group": which records are TLAS items
-        s->block_by_slot[b] = false;                  // until the slot-order copy below
+        blk.by_slot = false;                  // until the slot-order copy below
         // records: the instances, then (LBVH, option "group") the groups as instances of their merged BLAS
         const size_t nrec = s->inst.size() + s->groups.size();
         // only the changed records cross PCIe: (index, shift, cos / sin of the angles, scale, local box, inactive)
@@ -105,7 +108,7 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
             d.p.pad[0] = record_inactive(s, i) ? 1.0f : 0.0f;
             d.p.pad[1] = dev_bounded_rec(s, i) ? 1.0f : 0.0f;   // RT_TRI_UPDATE_BOUNDS
         }
-        uint8_t *fd = s->frame_dev[b];
+        uint8_t *fd = blk.dev;
         uint32_t live = 0;                              // records in this frame's TLAS
         for (size_t i = 0; i < nrec; i++) live += record_inactive(s, i) ? 0u : 1u;
         const bool small = s->tlas_small && live > 0 && live <= SMALL_TLAS_MAX;
@@ -124,16 +127,16 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
         // being written ("blas_double") or rewrites them in place, and a later frame on another lane stream that
         // builds nothing would otherwise read them mid-build (rt_scene_update_triangles once, a group break)
         if (cs != s->stream && s->blas_build_seq != 0) RT_TRY(wait_blas_built(s, cs));
-        if (s->r_used[b]) HIP_TRY(hipStreamWaitEvent(cs, s->r_used[b], 0));      // block b no longer read
+        if (blk.r_used) HIP_TRY(hipStreamWaitEvent(cs, blk.r_used, 0));      // block b no longer read
         RT_TRY(wait_queries(s, cs));
         // Instance::updateTransformArguments for every record of block b, on the GPU, with its BLAS root
         // (instances.hip); the deltas are read from the pinned staging block directly
-        HIP_TRY(launch_instance_update(reinterpret_cast<const InstDelta *>(s->staging_dev[si] + s->off_delta), nd,
+        HIP_TRY(launch_instance_update(reinterpret_cast<const InstDelta *>(stage.dev + s->off_delta), nd,
                                        s->inst_params.p + (size_t)b * n, n,
                                        reinterpret_cast<InstHot *>(fd + s->off_hot), reinterpret_cast<InstCold *>(fd + s->off_cold),
                                        reinterpret_cast<float *>(fd + s->off_tbox), reinterpret_cast<float4 *>(fd + s->off_tcent),
                                        s->inst_blas.p, s->cur.roots.p, s->blas_wide_refs.p, s->ib_cent.p, /*inf_inactive=*/!small, cs));
-        s->chain_stream[b] = cs;
+        blk.chain = cs;
         if (small) {
             // one workgroup: the LBVH TLAS over the live records, quads, slots, slot-ordered records (lbvh_tlas_small.hpp)
             SmallTlasArgs a{};
@@ -147,17 +150,17 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
             a.pair_count = s->gpu_counts.p + 2 + b;
             a.leaf_cap = s->tlas_leaf;
             HIP_TRY(launch_tlas_small(a, cs));
-            s->block_by_slot[b] = s->inst_by_slot;
+            blk.by_slot = s->inst_by_slot;
             // the trace indexes the slot-ordered copy (live records) or, without "inst_by_slot", the record-order
             // array, whose TLAS slots hold record indices up to n - 1 (lds_scene copies instance_count records)
-            s->frame_items[b] = s->inst_by_slot ? live : n;
-            HIP_TRY(hipEventRecord(s->ev_copied[b], cs));
-            s->r_copied[b] = s->r_staged[si] = s->ev_copied[b];
+            blk.items = s->inst_by_slot ? live : n;
+            HIP_TRY(hipEventRecord(blk.ev_copied, cs));
+            blk.r_copied = stage.r_staged = blk.ev_copied;
             s->active = b;
             s->frame = frame;
             return RT_OK;
         }
-        s->frame_items[b] = n;
+        blk.items = n;
         HIP_TRY(s->tlas_builder->set_items(reinterpret_cast<const float *>(fd + s->off_tbox),
                                            reinterpret_cast<const float4 *>(fd + s->off_tcent)));
         HIP_TRY(s->tlas_builder->build(reinterpret_cast<NodePair *>(fd + s->off_pairs), reinterpret_cast<TreeRoot *>(fd + s->off_root),
@@ -173,10 +176,10 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
                                                reinterpret_cast<const InstCold *>(fd + s->off_cold), n,
                                                reinterpret_cast<InstHot *>(fd + s->off_hot_s),
                                                reinterpret_cast<InstCold *>(fd + s->off_cold_s), s->stream));
-            s->block_by_slot[b] = true;
+            blk.by_slot = true;
         }
-        HIP_TRY(hipEventRecord(s->ev_copied[b], s->stream));
-        s->r_copied[b] = s->r_staged[si] = s->ev_copied[b];
+        HIP_TRY(hipEventRecord(blk.ev_copied, s->stream));
+        blk.r_copied = stage.r_staged = blk.ev_copied;
         s->active = b;
         s->frame = frame;
         return RT_OK;
@@ -220,8 +223,8 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
     std::memcpy(st + s->off_slots, s->tlas.refs.data(), s->tlas.refs.size() * sizeof(uint32_t));
     // instance records in TLAS leaf-slot order (SceneGPU::inst_by_slot): record j = the instance in slot j
     const size_t nrec = s->inst_by_slot ? s->tlas.refs.size() : s->inst.size() + s->groups.size();
-    s->block_by_slot[b] = s->inst_by_slot;
-    s->frame_items[b] = (uint32_t)nrec;
+    blk.by_slot = s->inst_by_slot;
+    blk.items = (uint32_t)nrec;
     for (size_t j = 0; j < nrec; j++) {
         const size_t id = s->inst_by_slot ? s->tlas.refs[j] : j;
         const InstState &in = id < s->inst.size() ? s->inst[id] : s->groups[id - s->inst.size()].st;
@@ -236,15 +239,15 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
     // Measured: the upload on a dedicated copy stream (the reference's copyStream, Renderer.cu:281-303)
     // went through an SDMA engine whose first use stalled a frame by ~7.6 ms; enqueued on the trace's
     // stream it is a ~4 us blit kernel between two traces.
-    HIP_TRY(hipStreamWaitEvent(upload, s->r_used[b], 0));            // frame_dev[b] free on device
+    HIP_TRY(hipStreamWaitEvent(upload, blk.r_used, 0));            // the block free on device
     RT_TRY(wait_queries(s, upload));
     if (defer) {
         s->pending_copy = b;
         s->pending_stage = si;
     } else {
-        HIP_TRY(hipMemcpyAsync(s->frame_dev[b], st, s->frame_block, hipMemcpyHostToDevice, upload));
-        HIP_TRY(hipEventRecord(s->ev_copied[b], upload));
-        s->r_copied[b] = s->r_staged[si] = s->ev_copied[b];
+        HIP_TRY(hipMemcpyAsync(blk.dev, st, s->frame_block, hipMemcpyHostToDevice, upload));
+        HIP_TRY(hipEventRecord(blk.ev_copied, upload));
+        blk.r_copied = stage.r_staged = blk.ev_copied;
     }
     s->active = b;
     s->frame = frame;
@@ -253,12 +256,12 @@ rt_status frame_update(rt_scene *s, uint64_t frame, hipStream_t upload, bool def
 
 SceneGPU scene_gpu(const rt_scene *s) {
     SceneGPU g{};
-    const int b = s->active;
+    const FrameBlock &blk = s->blk[s->active];
     g.blas_pairs = s->cur.pairs.p;
-    g.tlas_pairs = reinterpret_cast<const NodePair *>(s->frame_dev[b] + s->off_pairs);
-    g.tlas_root = reinterpret_cast<const TreeRoot *>(s->frame_dev[b] + s->off_root);
-    g.tlas_root_wide = reinterpret_cast<const TreeRoot *>(s->frame_dev[b] + s->off_root_wide);
-    g.tlas_quads = reinterpret_cast<const NodeQuad *>(s->frame_dev[b] + s->off_quads);
+    g.tlas_pairs = reinterpret_cast<const NodePair *>(blk.dev + s->off_pairs);
+    g.tlas_root = reinterpret_cast<const TreeRoot *>(blk.dev + s->off_root);
+    g.tlas_root_wide = reinterpret_cast<const TreeRoot *>(blk.dev + s->off_root_wide);
+    g.tlas_quads = reinterpret_cast<const NodeQuad *>(blk.dev + s->off_quads);
     g.blas_quads = s->cur.quads.p;
     // quad trees (GPU-built: from collapse_wide): 1 = host SAH BLASes collapsed greedily, visited by entry t; 2 = two
     // binary levels per quad visited in the reference's order (GPU-built trees); 3 = the same with every box decision
@@ -267,17 +270,17 @@ SceneGPU scene_gpu(const rt_scene *s) {
     g.wide = s->wide && s->cur.quads.p != nullptr
                  ? (s->quad_halves() ? ((s->build_mode == RT_BUILD_COMPAT_MEDIAN || s->exact_decisions) ? 3u : 2u) : 1u)
                  : 0u;
-    g.tlas_slots = reinterpret_cast<const uint32_t *>(s->frame_dev[b] + s->off_slots);
-    const bool gpu_slots = s->gpu_tlas() && s->block_by_slot[b];   // the slot-ordered copies of GPU-built frames
-    g.inst_hot = reinterpret_cast<const InstHot *>(s->frame_dev[b] + (gpu_slots ? s->off_hot_s : s->off_hot));
-    g.inst_cold = reinterpret_cast<const InstCold *>(s->frame_dev[b] + (gpu_slots ? s->off_cold_s : s->off_cold));
-    g.inst_by_slot = s->block_by_slot[b] ? 1u : 0u;   // how frame block b's instance records were staged
+    g.tlas_slots = reinterpret_cast<const uint32_t *>(blk.dev + s->off_slots);
+    const bool gpu_slots = s->gpu_tlas() && blk.by_slot;   // the slot-ordered copies of GPU-built frames
+    g.inst_hot = reinterpret_cast<const InstHot *>(blk.dev + (gpu_slots ? s->off_hot_s : s->off_hot));
+    g.inst_cold = reinterpret_cast<const InstCold *>(blk.dev + (gpu_slots ? s->off_cold_s : s->off_cold));
+    g.inst_by_slot = blk.by_slot ? 1u : 0u;   // how frame block b's instance records were staged
     g.tri_hot = s->cur.tri_hot.p; g.tri_cold = s->raw_shading() ? nullptr : s->cur.tri_cold.p;
     g.raw_tris = s->raw_shading() ? s->raw_tris.p : nullptr;
     g.sph_hot = s->cur.sph_hot.p; g.sph_cold = s->cur.sph_cold.p;
     g.quad_hot = s->cur.quad_hot.p; g.quad_cold = s->cur.quad_cold.p;
     g.materials = s->materials.p;
-    g.instance_count = s->frame_items[b];   // records the frame's TLAS holds (GPU-built, small path: the live ones)
+    g.instance_count = blk.items;   // records the frame's TLAS holds (GPU-built, small path: the live ones)
     g.rough_count = (uint32_t)s->roughs.size();
     g.material_count = (uint32_t)(s->materials.n / 4);
     // fixed setting "lds_scene" (an option until round 5): the quads the frame's TLAS refs can index (host-built: this frame's quad count;

@@ -3,8 +3,26 @@
 // event record costs, so a step moves as a whole or not at all.
 #include "launch.hpp"
 #include "scene.hpp"
+#include "sched_phase.hpp"
 
 namespace {
+
+// The call's checks and its options: the caller's or the defaults; a multi-GPU frame takes its tiling from the
+// communicator.
+rt_status frame_options(const rt_scene *s, const rt_render_opts *opts, const float *rgb_host, rt_render_opts &o) {
+    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "null scene");
+    if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
+    if (!s->cam_ok) return fail(RT_ERR_STATE, "rt_camera_set has not been called");
+    if (opts) o = *opts;
+    if (o.frame_seed == 0) o.frame_seed = 0x5EED;
+    if (const CommState *cm = s->comm) {       // multi-GPU frame: the communicator owns the tiling
+        if (o.tile_count) return fail(RT_ERR_INVALID_ARGUMENT, "tile options are set by rt_scene_attach_comm");
+        if (o.rgb32_device || rgb_host) return fail(RT_ERR_UNSUPPORTED, "rgb32 outputs are not gathered across ranks");
+        o.tile_w = cm->tile_w; o.tile_h = cm->tile_h;
+        o.tile_rank = (uint32_t)cm->rank; o.tile_count = (uint32_t)cm->world;
+    }
+    return RT_OK;
+}
 
 // a trace that skipped the frame update after rt_scene_update_triangles would traverse the old trees while its hits
 // read the new triangles (raw_tris): the next frame update rebuilds the BLASes first
@@ -39,7 +57,7 @@ rt_status auto_lanes(rt_scene *s, const rt_render_opts &o) {
 rt_status frame_stream(rt_scene *s, const rt_render_opts &o, hipStream_t *stream) {
     *stream = static_cast<hipStream_t>(o.stream);
     if (!*stream && s->overlap) {
-        hipStream_t &ls = s->lane_st[s->lane];
+        hipStream_t &ls = s->ln[s->lane].st;
         if (!ls) {
             int lo = 0, hi = 0;                    // option "lane_priority": 1 = the device's highest stream priority
             HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -101,10 +119,7 @@ rt_status frame_outputs(rt_scene *s, const rt_render_opts &o, int q, size_t npix
         }
         DevBuf<uint8_t> &buf = cm->rank == 0 ? cm->gathered[q] : cm->slab[q];
         const size_t need = cm->rank == 0 ? slab_bytes * (size_t)cm->world : slab_bytes;
-        if (!buf.p) {                          // slab padding is never assembled: no clearing needed
-            HIP_TRY(hipMalloc(&buf.p, need));
-            buf.n = need;
-        }
+        if (!buf.p) HIP_TRY(buf.alloc(need));  // need > 0; slab padding is never assembled: no clearing needed
         out.rgba = buf.p;                      // rank 0: slab 0 of the gather buffer
         if (cm->rank == 0) {
             if (o.rgba8_device) {
@@ -156,7 +171,7 @@ uint32_t persistent_grid(const rt_scene *s, int q, uint32_t cap, uint64_t paths)
     if (pct == 0) {
         bool partner = false;             // another lane's launch not finished yet (host query, ~1 us)
         for (int l = 0; s->overlap && l < rt_scene::NLANE && !partner; l++)
-            partner = l != q && s->r_lane[l] && hipEventQuery(s->r_lane[l]) == hipErrorNotReady;
+            partner = l != q && s->ln[l].r_done && hipEventQuery(s->ln[l].r_done) == hipErrorNotReady;
         // with a partner: half the GPU for up to 3 lanes, 1 / lanes + 12 % of it with more (4 lanes: 37 %, 8 lanes:
         // 24 %: the measured best for a whole frame on 4 lanes and for a rank's 1/2, 1/4 and 1/8 share once every
         // lane runs off the null stream: C2 0.173 -> 0.164 ms/frame, C2 1/8 share 0.041 -> 0.038, 1/4 0.059 ->
@@ -177,25 +192,180 @@ uint32_t persistent_grid(const rt_scene *s, int q, uint32_t cap, uint64_t paths)
 rt_status frame_counters(rt_scene *s, uint32_t flags, int q, hipStream_t stream) {
     const bool sum_lanes = s->overlap && (flags & RT_RENDER_KEEP_COUNTERS);
     if (!sum_lanes)
-        HIP_TRY(hipMemcpyAsync(s->counters_host, s->counters + (size_t)q * CNT_NUM, CNT_NUM * sizeof(unsigned long long),
+        HIP_TRY(hipMemcpyAsync(s->counters_host, s->lane_counters(q), CNT_NUM * sizeof(unsigned long long),
                                hipMemcpyDeviceToHost, stream));
     RT_TRY(wait_stream(s, stream));
     if (sum_lanes) {
-        RT_TRY(drain(s));
-        HIP_TRY(hipMemcpy(s->counters_host, s->counters, rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost));
-        for (int l = 1; l < rt_scene::NLANE; l++)          // lane blocks of the current epoch, summed into block 0
-            for (uint32_t k = 0; k < CNT_NUM; k++) {
-                if (l == 1 && s->lane_epoch[0] != s->cnt_epoch) s->counters_host[k] = 0;
-                if (s->lane_epoch[l] == s->cnt_epoch) s->counters_host[k] += s->counters_host[(size_t)l * CNT_NUM + k];
-            }
+        unsigned long long sum[CNT_NUM];       // a lane 0 out of the epoch counts as little as any other
+        RT_TRY(sum_lane_counters(s, sum));
+        std::memcpy(s->counters_host, sum, sizeof sum);
     }
+    return RT_OK;
+}
+
+// What this launch's prologue has done so far.  The prologue is the kernel in front of the trace (the schedule kernel,
+// else the frame-copy kernel) that also performs the frame block's deferred upload, clears the lane's counter block
+// and resets its queue heads: each of the three once per launch, by the first prologue kernel there is.
+struct Prologue {
+    unsigned long long *counters;   // the lane's counter block: only this lane's launches add here
+    uint32_t *queue;                // the lane's queue heads (null: no persistent kernel)
+    bool zero_lane;                 // the counter block is still to clear (the lane's first launch in the counter epoch)
+    bool reset_queue = true;        // the queue heads are still to reset
+    bool copied_here = false;       // this call enqueued the frame block's upload on `stream`
+    // ... of this frame block: no event between the copy and the trace (each event record between two kernels
+    // of a stream costs ~4.5 us of GPU idle: copy -> trace gap 10.6 -> 6.1 us, profiles/r02_gaps.txt); its
+    // r_copied is the trace's completion event (the host waits on it only before reusing the staging buffer)
+    int copied_block = -1, copied_stage = -1;
+};
+
+// What one prologue kernel takes on, struck off the list: the pending upload (frame_update with `defer`; consumed
+// here and nowhere else), the counter block, the queue heads.
+struct PrologueWork {
+    uint8_t *dst = nullptr;
+    const uint8_t *src = nullptr;
+    size_t bytes = 0;
+    unsigned long long *zero = nullptr;
+    uint32_t *queue = nullptr;
+};
+PrologueWork take_prologue(rt_scene *s, Prologue &p) {
+    PrologueWork w;
+    if (s->pending_copy >= 0) {
+        w.dst = s->blk[s->pending_copy].dev;
+        w.src = s->stg[s->pending_stage].dev;
+        w.bytes = s->frame_block;
+        p.copied_here = true;
+        p.copied_block = s->pending_copy;
+        p.copied_stage = s->pending_stage;
+        s->pending_copy = -1;
+    }
+    if (p.zero_lane) w.zero = p.counters;
+    if (p.reset_queue) w.queue = p.queue;
+    p.zero_lane = p.reset_queue = false;
+    return w;
+}
+
+// Option "reorder" (schedule.hip; persistent kernel, 64-pixel claims): the lane's schedule step in front of its launch.
+// The schedule kernel, when it runs, is the launch's prologue and resets the queue heads itself.
+rt_status schedule_step(rt_scene *s, Lane &ln, OutputGPU &out, Prologue &pro, hipStream_t stream) {
+    if (ln.unit_cost.n < 2 * (size_t)out.units) {         // [recorded costs | costs of the last launch (debug)]
+        ln.unit_order.release();                          // sized with the costs, whatever it held
+        HIP_TRY(ln.unit_cost.reserve(2 * (size_t)out.units));
+        HIP_TRY(hipMemsetAsync(ln.unit_cost.p, 0, ln.unit_cost.n * sizeof(uint32_t), stream));
+        HIP_TRY(ln.unit_order.reserve(4 * (size_t)out.units));   // <= 4 items per unit
+        ln.valid = false;
+    }
+    const uint32_t sig[7] = {out.units, out.units_x, out.tile_w, out.tile_h, out.tile_rank, out.tile_count,
+                             out.queue_parts};
+    // the costs the lane's previous launch recorded are for the layout it had
+    const bool layout_ok = ln.valid && std::memcmp(sig, ln.sig, sizeof sig) == 0;
+    const SchedStep d = sched_step(layout_ok, s->reorder_period, ln.phase);
+    ln.phase = d.phase;
+    if (d.drop_order) ln.order_ok = false;
+    if (d.run_sched) {
+        const uint32_t rows = out.tile_count == 0 ? out.units / out.units_x : out.units;
+        const uint32_t upr = out.tile_count == 0 ? out.units_x : 1u;
+        const PrologueWork w = take_prologue(s, pro);
+        HIP_TRY(launch_schedule(ln.unit_cost.p, ln.unit_cost.p + out.units, ln.unit_order.p, ln.queue, rows, upr, out.queue_parts,
+                                d.do_order, s->split & 0xFFu, (s->split >> 8) & 0xFFu, s->merge, w.dst, w.src, w.bytes, w.zero,
+                                stream));
+        if (d.do_order) ln.order_ok = true;
+    }
+    std::memcpy(ln.sig, sig, sizeof sig);
+    ln.valid = true;
+    out.order = ln.order_ok ? ln.unit_order.p : nullptr;
+    out.unit_cost = d.track ? ln.unit_cost.p : nullptr;
+    return RT_OK;
+}
+
+// What the launch waits for on its stream before its prologue: the previous launch of its lane, and the caller's
+// null-stream work.
+rt_status lane_waits(rt_scene *s, int q, bool order_null, hipStream_t stream) {
+    if (hipEvent_t prev = s->overlap ? s->ln[q].r_done : s->r_done) HIP_TRY(hipStreamWaitEvent(stream, prev, 0));
+    // Device outputs and no stream: the trace runs on a non-blocking stream of the scene, which HIP does not order
+    // with the caller's null-stream work, so it waits for what the caller enqueued there before the call (e.g. a fill
+    // of the buffer), and — without "overlap" — the null stream waits for the frame (a read of it after the call).  The
+    // reference draws into a surface it owns on its own stream (Renderer.cu:305-317), so a drop-in caller expects no
+    // ordering of its own.  With "overlap" the frames run side by side on the scene's lanes; a null-stream wait per
+    // frame would serialise them, so their device outputs are complete once rt_synchronize returns.
+    // (A null stream with nothing pending needs no wait: one host query instead of a cross-queue wait, ~5 us of GPU
+    // idle time per frame, profiles/r02_gaps.txt.)
+    if (order_null && hipStreamQuery(nullptr) == hipErrorNotReady) RT_TRY(order_after_null_stream(s, stream));
+    return RT_OK;
+}
+
+// The launch's prologue: the schedule step, the frame block's upload or the wait for it, the lane's resets.
+rt_status frame_prologue(rt_scene *s, Lane &ln, OutputGPU &out, Prologue &pro, hipStream_t stream) {
+    if (s->use_persistent && s->reorder && s->grab == 64u) RT_TRY(schedule_step(s, ln, out, pro, stream));
+    const bool upload = s->pending_copy >= 0;
+    const FrameBlock &blk = s->blk[s->active];
+    // the frame block's upload: stream-ordered when this call enqueues it
+    if (!upload && !pro.copied_here && !(s->gpu_tlas() && blk.chain == stream))   // else built on this stream
+        HIP_TRY(hipStreamWaitEvent(stream, blk.r_copied, 0));
+    // the frame block's upload (and the lane's counter / queue reset); GPU-built frames: one small kernel instead of
+    // two fills
+    if (upload || pro.zero_lane || (pro.reset_queue && pro.queue)) {
+        const PrologueWork w = take_prologue(s, pro);
+        HIP_TRY(launch_frame_copy(w.dst, w.src, w.bytes, w.zero, w.queue, stream));
+    }
+    return RT_OK;
+}
+
+// The trace, between the timing events of its ring slot.
+rt_status launch_trace(rt_scene *s, int q, uint32_t flags, const SceneGPU &g, const CameraGPU &cam, const OutputGPU &out,
+                       const Prologue &pro, hipStream_t stream, uint32_t *ring_slot) {
+    const bool exact = (flags & RT_RENDER_EXACT) != 0;
+    const bool count = (flags & RT_RENDER_COUNT_WORK) != 0;
+    const TraceFlavour &kernels = trace_flavour(exact, s->fast_math);
+    const uint32_t slot = s->ring_head;
+    s->ring_head = (s->ring_head + 1) % rt_scene::RING;
+    if (s->ring_pending < rt_scene::RING) s->ring_pending++;
+    s->last_stream = stream;
+    HIP_TRY(hipEventRecord(s->ring_start[slot], stream));
+    if (s->use_persistent) {
+        const uint32_t cap = s->cus * persistent_blocks_per_cu(exact, s->fast_math, g);
+        const uint32_t blocks = persistent_grid(s, q, cap, (uint64_t)out.units * 64u * cam.sqrt_s * cam.sqrt_s);
+        const uint32_t thr = s->threshold ? s->threshold : (cam.depth * cam.sqrt_s * cam.sqrt_s <= 2u ? 64u : 40u);
+        HIP_TRY(kernels.render_persistent(g, cam, out, count, pro.counters, pro.queue, blocks, thr, pro.reset_queue, stream));
+    } else {
+        HIP_TRY(kernels.render(g, cam, out, count, pro.counters, stream));
+    }
+    HIP_TRY(hipEventRecord(s->ring_stop[slot], stream));
+    *ring_slot = slot;
+    return RT_OK;
+}
+
+// The launch's one completion event (see FrameBlock::r_used) and every purpose it completes.
+rt_status complete_launch(rt_scene *s, int q, uint32_t slot, const Prologue &pro, uint8_t *frame_out, bool null_waits,
+                          hipStream_t stream) {
+    hipEvent_t done = s->ring_stop[slot];
+    if (s->comm) {                             // after the gather + assemble; one event per launch, never one
+        RT_TRY(comm_gather(s, q, frame_out, stream));
+        HIP_TRY(hipEventRecord(s->ring_post[slot], stream));   // re-recorded by the lane's next frame (the
+        done = s->ring_post[slot];                              // staging / block waits must see this launch)
+    }
+    s->blk[s->active].r_used = s->r_done = s->ln[q].r_done = done;
+    if (pro.copied_block >= 0) s->blk[pro.copied_block].r_copied = s->stg[pro.copied_stage].r_staged = done;
+    if (s->cur.ev_lane[q]) HIP_TRY(hipEventRecord(s->cur.ev_lane[q], stream));   // "blas_double": this set's reader
+    if (null_waits) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
     return RT_OK;
 }
 
 }  // namespace
 
 namespace rtamd {
+
+// The counters of every lane whose block belongs to the current epoch, summed (rt_scene_collect, frame_counters),
+// after every launch of the scene finished; counters_host holds the lanes' blocks afterwards.
+rt_status sum_lane_counters(rt_scene *s, unsigned long long *sum) {
+    RT_TRY(drain(s));
+    HIP_TRY(hipMemcpy(s->counters_host, s->counters, rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long),
+                      hipMemcpyDeviceToHost));
+    std::fill(sum, sum + CNT_NUM, 0ull);
+    for (int l = 0; l < rt_scene::NLANE; l++)
+        if (s->ln[l].epoch == s->cnt_epoch)
+            for (uint32_t k = 0; k < CNT_NUM; k++) sum[k] += s->counters_host[(size_t)l * CNT_NUM + k];
+    return RT_OK;
+}
 
 // a caller buffer kernels on `device` may touch: device memory of that device, managed memory, or mapped host memory
 bool device_accessible(const void *p, int device) {
@@ -217,21 +387,11 @@ extern "C" {
 rt_status rt_render(rt_scene *s, uint64_t frame, const rt_render_opts *opts, uint8_t *rgba_host, float *rgb_host,
                     rt_stats *stats) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "null scene");
-    if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
-    if (!s->cam_ok) return fail(RT_ERR_STATE, "rt_camera_set has not been called");
     rt_render_opts o{};
-    if (opts) o = *opts;
-    if (o.frame_seed == 0) o.frame_seed = 0x5EED;
-    CommState *cm = s->comm;
-    if (cm) {                                  // multi-GPU frame: the communicator owns the tiling
-        if (o.tile_count) return fail(RT_ERR_INVALID_ARGUMENT, "tile options are set by rt_scene_attach_comm");
-        if (o.rgb32_device || rgb_host) return fail(RT_ERR_UNSUPPORTED, "rgb32 outputs are not gathered across ranks");
-        o.tile_w = cm->tile_w; o.tile_h = cm->tile_h;
-        o.tile_rank = (uint32_t)cm->rank; o.tile_count = (uint32_t)cm->world;
-    }
+    RT_TRY(frame_options(s, opts, rgb_host, o));
     if ((o.flags & RT_RENDER_SKIP_UPDATE) && s->blas_dirty) return fail_blas_dirty();
     HIP_TRY(hipSetDevice(s->device));
+    // the lanes, the stream, the frame update
     if (s->overlap_auto) RT_TRY(auto_lanes(s, o));
     hipStream_t stream = nullptr;
     RT_TRY(frame_stream(s, o, &stream));
@@ -256,10 +416,6 @@ rt_status rt_render(rt_scene *s, uint64_t frame, const rt_render_opts *opts, uin
     CameraGPU cam = s->cam;
     cam.frame_seed = o.frame_seed;
     const SceneGPU g = scene_gpu(s);
-    const bool exact = (o.flags & RT_RENDER_EXACT) != 0;
-    const bool count = (o.flags & RT_RENDER_COUNT_WORK) != 0;
-    const TraceFlavour &kernels = trace_flavour(exact, s->fast_math);
-
     if (s->use_persistent) {
         out.queue_parts = s->queue_parts;
         out.grab = s->grab;
@@ -268,125 +424,25 @@ rt_status rt_render(rt_scene *s, uint64_t frame, const rt_render_opts *opts, uin
     }
     s->lane = s->overlap ? (s->lane + 1) % s->lanes : 0u;
     s->last_lane = q;
-    if (hipEvent_t prev = s->overlap ? s->r_lane[q] : s->r_done) HIP_TRY(hipStreamWaitEvent(stream, prev, 0));
-    // Device outputs and no stream: the trace runs on a non-blocking stream of the scene, which HIP does not order
-    // with the caller's null-stream work, so it waits for what the caller enqueued there before the call (e.g. a fill
-    // of the buffer), and — without "overlap" — the null stream waits for the frame (a read of it after the call).  The
-    // reference draws into a surface it owns on its own stream (Renderer.cu:305-317), so a drop-in caller expects no
-    // ordering of its own.  With "overlap" the frames run side by side on the scene's lanes; a null-stream wait per
-    // frame would serialise them, so their device outputs are complete once rt_synchronize returns.
-    // (A null stream with nothing pending needs no wait: one host query instead of a cross-queue wait, ~5 us of GPU
-    // idle time per frame, profiles/r02_gaps.txt.)
+    // the waits, the prologue (schedule, upload, resets), the trace, its completion event
     const bool order_null = !o.stream && (o.rgba8_device || o.rgb32_device);
-    if (order_null && hipStreamQuery(nullptr) == hipErrorNotReady) RT_TRY(order_after_null_stream(s, stream));
-    unsigned long long *lane_counters = s->counters + (size_t)q * CNT_NUM;   // only this lane's launches add here
+    RT_TRY(lane_waits(s, q, order_null, stream));
+    Lane &ln = s->ln[q];
     if (!(o.flags & RT_RENDER_KEEP_COUNTERS)) s->cnt_epoch++;
-    bool zero_lane = s->lane_epoch[q] != s->cnt_epoch;                      // cleared before this launch
-    s->lane_epoch[q] = s->cnt_epoch;
-    bool reset_queue = true;
-    bool copied_here = false;                  // this call enqueued the frame block's upload on `stream`
-    // ... of this frame block: no event between the copy and the trace (each event record between two kernels
-    // of a stream costs ~4.5 us of GPU idle: copy -> trace gap 10.6 -> 6.1 us, profiles/r02_gaps.txt); its
-    // r_copied is the trace's completion event (the host waits on it only before reusing the staging buffer)
-    int copied_block = -1, copied_stage = -1;
-    if (s->use_persistent && s->reorder && s->grab == 64u) {
-        DevBuf<uint32_t> &unit_cost = s->unit_cost[q], &unit_order = s->unit_order[q];
-        if (unit_cost.n < 2 * (size_t)out.units) {        // [recorded costs | costs of the last launch (debug)]
-            unit_order.release();                         // sized with the costs, whatever it held
-            HIP_TRY(unit_cost.reserve(2 * (size_t)out.units));
-            HIP_TRY(hipMemsetAsync(unit_cost.p, 0, unit_cost.n * sizeof(uint32_t), stream));
-            HIP_TRY(unit_order.reserve(4 * (size_t)out.units));   // <= 4 items per unit
-            s->sched_valid[q] = false;
-        }
-        const uint32_t sig[7] = {out.units, out.units_x, out.tile_w, out.tile_h, out.tile_rank, out.tile_count,
-                                 out.queue_parts};
-        // the costs the lane's previous launch recorded are for the layout it had
-        const bool layout_ok = s->sched_valid[q] && std::memcmp(sig, s->sched_sig[q], sizeof sig) == 0;
-        const uint32_t K = s->reorder_period;
-        uint32_t &ph = s->sched_phase[q];
-        // phase 0 records costs, phase 1 orders from them; K = 1: both on every launch.  A new layout
-        // starts over: the schedule kernel clears the costs and this launch records in screen order.
-        bool run_sched, track;
-        if (!layout_ok) {
-            run_sched = true; track = true; s->order_ok[q] = false; ph = K == 1 ? 0u : 1u;
-        } else if (K == 1) {
-            run_sched = true; track = true;
-        } else {
-            run_sched = ph == 1; track = ph == 0; ph = (ph + 1) % K;
-        }
-        const bool do_order = layout_ok && run_sched;
-        if (run_sched) {
-            const uint32_t rows = out.tile_count == 0 ? out.units / out.units_x : out.units;
-            const uint32_t upr = out.tile_count == 0 ? out.units_x : 1u;
-            const int pc = s->pending_copy;
-            HIP_TRY(launch_schedule(unit_cost.p, unit_cost.p + out.units, unit_order.p, s->queue[q], rows, upr, out.queue_parts,
-                                    do_order, s->split & 0xFFu, (s->split >> 8) & 0xFFu, s->merge,
-                                    pc >= 0 ? s->frame_dev[pc] : nullptr,
-                                    pc >= 0 ? s->staging_dev[s->pending_stage] : nullptr, pc >= 0 ? s->frame_block : 0,
-                                    zero_lane ? lane_counters : nullptr, stream));
-            zero_lane = false;
-            copied_here = pc >= 0;
-            copied_block = pc;
-            copied_stage = s->pending_stage;
-            s->pending_copy = -1;
-            if (do_order) s->order_ok[q] = true;
-            reset_queue = false;
-        }
-        std::memcpy(s->sched_sig[q], sig, sizeof sig);
-        s->sched_valid[q] = true;
-        out.order = s->order_ok[q] ? unit_order.p : nullptr;
-        out.unit_cost = track ? unit_cost.p : nullptr;
-    }
-    if (s->pending_copy >= 0) {                // the frame block's upload (and the lane's counter / queue reset)
-        HIP_TRY(launch_frame_copy(s->frame_dev[s->pending_copy], s->staging_dev[s->pending_stage], s->frame_block,
-                                  zero_lane ? lane_counters : nullptr, reset_queue && s->use_persistent ? s->queue[q] : nullptr,
-                                  stream));
-        copied_block = s->pending_copy;
-        copied_stage = s->pending_stage;
-        s->pending_copy = -1;
-        zero_lane = false;
-        reset_queue = false;
-        copied_here = true;
-    }
-    // the frame block's upload: stream-ordered when this call enqueued it
-    if (!copied_here && !(s->gpu_tlas() && s->chain_stream[s->active] == stream))   // else built on this stream
-        HIP_TRY(hipStreamWaitEvent(stream, s->r_copied[s->active], 0));
-    if (zero_lane || (reset_queue && s->use_persistent)) {   // GPU-built frames: one small kernel instead of two fills
-        HIP_TRY(launch_frame_copy(nullptr, nullptr, 0, zero_lane ? lane_counters : nullptr,
-                                  reset_queue && s->use_persistent ? s->queue[q] : nullptr, stream));
-        zero_lane = false;
-        if (s->use_persistent) reset_queue = false;
-    }
-    const uint32_t slot = s->ring_head;
-    s->ring_head = (s->ring_head + 1) % rt_scene::RING;
-    if (s->ring_pending < rt_scene::RING) s->ring_pending++;
-    s->last_stream = stream;
-    HIP_TRY(hipEventRecord(s->ring_start[slot], stream));
-    if (s->use_persistent) {
-        const uint32_t cap = s->cus * persistent_blocks_per_cu(exact, s->fast_math, g);
-        const uint32_t blocks = persistent_grid(s, q, cap, (uint64_t)out.units * 64u * cam.sqrt_s * cam.sqrt_s);
-        const uint32_t thr = s->threshold ? s->threshold : (cam.depth * cam.sqrt_s * cam.sqrt_s <= 2u ? 64u : 40u);
-        HIP_TRY(kernels.render_persistent(g, cam, out, count, lane_counters, s->queue[q], blocks, thr, reset_queue, stream));
-    } else {
-        HIP_TRY(kernels.render(g, cam, out, count, lane_counters, stream));
-    }
-    HIP_TRY(hipEventRecord(s->ring_stop[slot], stream));
-    hipEvent_t done = s->ring_stop[slot];      // the launch's one completion event (see r_used)
-    if (cm) {                                  // after the gather + assemble; one event per launch, never one
-        RT_TRY(comm_gather(s, q, frame_out, stream));
-        HIP_TRY(hipEventRecord(s->ring_post[slot], stream));   // re-recorded by the lane's next frame (the
-        done = s->ring_post[slot];                              // staging / block waits must see this launch)
-    }
-    s->r_used[s->active] = s->r_done = s->r_lane[q] = done;
-    if (copied_block >= 0) s->r_copied[copied_block] = s->r_staged[copied_stage] = done;
-    if (s->cur.ev_lane[q]) HIP_TRY(hipEventRecord(s->cur.ev_lane[q], stream));   // "blas_double": this set's reader
-    if (order_null && !lib_lane) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
+    Prologue pro{s->lane_counters(q), s->use_persistent ? ln.queue : nullptr, /*zero_lane=*/ln.epoch != s->cnt_epoch};
+    ln.epoch = s->cnt_epoch;
+    RT_TRY(frame_prologue(s, ln, out, pro, stream));
+    uint32_t slot = 0;
+    RT_TRY(launch_trace(s, q, o.flags, g, cam, out, pro, stream, &slot));
+    RT_TRY(complete_launch(s, q, slot, pro, frame_out, order_null && !lib_lane, stream));
     if (o.flags & RT_RENDER_NO_SYNC) {
         if (stats) { std::memset(stats, 0, sizeof *stats); stats->update_ms = update_ms; stats->update_wait_ms = s->update_wait_ms; }
         return RT_OK;
     }
+    // a synchronous frame: its counters, its pixels, its statistics
     RT_TRY(frame_counters(s, o.flags, q, stream));
     s->ring_pending = 0;
+    const CommState *cm = s->comm;
     if (rgba_host && cm && cm->rank == 0)
         HIP_TRY(hipMemcpy(rgba_host, frame_out, (size_t)s->width * s->height * 4, hipMemcpyDeviceToHost));
     else if (rgba_host && !cm) HIP_TRY(hipMemcpy(rgba_host, out.rgba, npix * 4, hipMemcpyDeviceToHost));
@@ -400,7 +456,7 @@ rt_status rt_render(rt_scene *s, uint64_t frame, const rt_render_opts *opts, uin
         stats->update_wait_ms = s->update_wait_ms;
         stats->frame_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    if (count && s->counters_host[CNT_OVERFLOW] != 0)
+    if ((o.flags & RT_RENDER_COUNT_WORK) && s->counters_host[CNT_OVERFLOW] != 0)
         return fail(RT_ERR_UNSUPPORTED, "traversal stack overflow (tree deeper than 64 levels)");
     return RT_OK;
 }
@@ -437,11 +493,12 @@ rt_status rt_trace_rays(rt_scene *s, const float *rays, size_t n, uint32_t flags
     if (e != hipSuccess) { (void)hipFree(d_rays); return fail(RT_ERR_OUT_OF_MEMORY, "hipMalloc hits"); }
     const SceneGPU g = scene_gpu(s);
     e = hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->r_copied[s->active], 0);
+    FrameBlock &blk = s->blk[s->active];
+    if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, blk.r_copied, 0);
     if (e == hipSuccess)
         e = trace_flavour((flags & RT_RENDER_EXACT) != 0, s->fast_math).trace_rays(g, d_rays, (uint32_t)n, d_hits, s->stream);
-    if (e == hipSuccess) e = hipEventRecord(s->ev_used[s->active], s->stream);
-    if (e == hipSuccess) { s->r_used[s->active] = s->ev_used[s->active]; s->r_done = s->ev_used[s->active]; }
+    if (e == hipSuccess) e = hipEventRecord(blk.ev_used, s->stream);
+    if (e == hipSuccess) blk.r_used = s->r_done = blk.ev_used;
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e == hipSuccess) e = hipMemcpy(hits, d_hits, n * sizeof(rt_hit), hipMemcpyDeviceToHost);
     (void)hipFree(d_rays);
@@ -474,11 +531,11 @@ rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
     hipStream_t st = qy->stream ? static_cast<hipStream_t>(qy->stream) : s->stream;
     const uint32_t slot = s->query_next;       // advanced once the query is enqueued: a failed call takes no slot
     hipEvent_t done = s->ev_query[slot];
-    const int b = s->active;
+    FrameBlock &blk = s->blk[s->active];
     // What the launch waits for.  Its slot's previous query (head free; see ev_query) and the previous call's (queries
     // run in call order even with a frame's launch between them).  The frame block of the last
     // update, as a RT_RENDER_SKIP_UPDATE frame does, and a GPU BLAS build still running on the scene's stream.  And
-    // every event this call replaces below — r_used[b], r_done, the BLAS set's reader event: whoever waits on those
+    // every event this call replaces below — the block's r_used, r_done, the BLAS set's reader event: whoever waits on those
     // afterwards sees only this query, which runs on a caller stream and so implies nothing about the launches on the
     // lane streams they stood for.
     // An event that has already completed needs no wait (a host query, ~1 us, as wait_blas_built): whatever is enqueued
@@ -486,7 +543,7 @@ rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
     // purposes often share one event (a frame's single completion event): each is waited on once.
     const int bl = s->last_lane;
     hipEvent_t prev_query = s->ev_query[(slot + rt_scene::NQUERY - 1) % rt_scene::NQUERY];
-    hipEvent_t deps[] = {done, prev_query, s->r_copied[b], s->r_used[b], s->r_done, s->cur.ev_lane[bl]};
+    hipEvent_t deps[] = {done, prev_query, blk.r_copied, blk.r_used, s->r_done, s->cur.ev_lane[bl]};
     for (size_t i = 0; i < sizeof deps / sizeof deps[0]; i++) {
         bool dup = !deps[i];
         for (size_t j = 0; j < i && !dup; j++) dup = deps[j] == deps[i];
@@ -507,7 +564,7 @@ rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
     HIP_TRY(hipEventRecord(done, st));
     s->query_next = (slot + 1) % rt_scene::NQUERY;
     s->query_live = true;
-    s->r_used[b] = s->r_done = done;           // later uploads into block b, later BLAS rebuilds, rt_synchronize
+    blk.r_used = s->r_done = done;             // later uploads into the block, later BLAS rebuilds, rt_synchronize
     if (s->cur.ev_lane[bl]) HIP_TRY(hipEventRecord(s->cur.ev_lane[bl], st));   // "blas_double": this set's reader
     if (!qy->stream) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
     if (qy->flags & RT_QUERY_NO_SYNC) return RT_OK;

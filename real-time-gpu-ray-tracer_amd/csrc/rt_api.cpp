@@ -227,15 +227,14 @@ rt_status rt_scene_set_option(rt_scene *s, const char *key, int64_t value) {
     } else if (k == "lane_priority") {
         RT_TRY(boolean("lane_priority"));
         RT_TRY(drain(s));
-        for (hipStream_t &l : s->lane_st) {
-            if (!l) continue;
-            // nothing may keep a handle to a destroyed lane stream: drain() waits on last_stream, frame_update
-            // compares chain_stream[] with the frame's stream
-            if (s->last_stream == l) s->last_stream = nullptr;
-            for (hipStream_t &c : s->chain_stream)
-                if (c == l) c = nullptr;
-            (void)hipStreamDestroy(l);
-            l = nullptr;                                                // recreated at the next frame
+        for (Lane &l : s->ln) {
+            if (!l.st) continue;
+            // nothing may keep a handle to a destroyed lane stream: drain() waits on last_stream, rt_render and
+            // wait_record_chains compare each frame block's chain stream (FrameBlock::chain) with the frame's stream
+            if (s->last_stream == l.st) s->last_stream = nullptr;
+            for (FrameBlock &b : s->blk)
+                if (b.chain == l.st) b.chain = nullptr;
+            l.destroy_stream();                                         // recreated at the next frame
         }
         s->lane_priority = value == 1;
     } else if (k == "tlas_sah") {
@@ -250,7 +249,7 @@ rt_status rt_scene_set_option(rt_scene *s, const char *key, int64_t value) {
         s->lane = 0;
     } else if (k == "reorder") {
         RT_TRY(boolean("reorder"));
-        if (s->reorder != (value == 1)) for (bool &v : s->sched_valid) v = false;
+        if (s->reorder != (value == 1)) s->forget_schedules();
         s->reorder = value == 1;
     } else {
         return fail(RT_ERR_INVALID_ARGUMENT, "unknown option " + k);
@@ -262,16 +261,12 @@ rt_status rt_scene_collect(rt_scene *s, rt_stats *acc, float *kernel_ms, uint32_
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "null scene");
     if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
     HIP_TRY(hipSetDevice(s->device));
-    RT_TRY(drain(s));
-    HIP_TRY(hipMemcpy(s->counters_host, s->counters, rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long sum[CNT_NUM] = {};
-    for (int l = 0; l < rt_scene::NLANE; l++)          // lanes whose block belongs to the current epoch
-        if (s->lane_epoch[l] == s->cnt_epoch)
-            for (uint32_t k = 0; k < CNT_NUM; k++) sum[k] += s->counters_host[(size_t)l * CNT_NUM + k];
+    unsigned long long sum[CNT_NUM];
+    RT_TRY(sum_lane_counters(s, sum));
     if (acc) fill_stats(acc, sum);
     // collected: the next KEEP_COUNTERS frames accumulate from zero (every block is clear and current)
     HIP_TRY(hipMemset(s->counters, 0, rt_scene::NLANE * CNT_NUM * sizeof(unsigned long long)));
-    for (uint64_t &e : s->lane_epoch) e = s->cnt_epoch;
+    for (Lane &l : s->ln) l.epoch = s->cnt_epoch;
     const uint32_t n = s->ring_pending;
     uint32_t written = 0;
     for (uint32_t k = 0; k < n; k++) {
@@ -311,7 +306,7 @@ rt_status rt_scene_get_info(const rt_scene *s, rt_scene_info *info) {
         uint32_t np = 0;
         TreeRoot root{};
         HIP_TRY(hipMemcpy(&np, s->gpu_counts.p + 2 + s->active, sizeof np, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&root, s->frame_dev[s->active] + s->off_root, sizeof root, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&root, s->blk[s->active].dev + s->off_root, sizeof root, hipMemcpyDeviceToHost));
         info->tlas_node_pairs = np;
         info->tlas_height = root.height;
     }

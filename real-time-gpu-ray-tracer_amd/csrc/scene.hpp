@@ -1,7 +1,8 @@
 // scene.hpp — the scene's state (struct rt_scene) and the internal interface between the host files: the error and
 // wait discipline (scene_sync.cpp), the host half of a frame (frame.cpp), the acceleration-structure builds (build.cpp,
 // blas_gpu.cpp), the geometry updates (update.cpp), the RCCL path (scene_comm.cpp); render.cpp, debug.cpp and
-// rt_api.cpp only call into them.
+// rt_api.cpp only call into them.  What the scene keeps per overlap lane, per frame block and per staging buffer is
+// declared once each (Lane, FrameBlock, Stage), with the members that create, reset and release it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,12 +87,85 @@ struct InstGroup {
     bool valid = true;
 };
 
+// Overlap lanes, and as many frame blocks: frame blocks cycle through NLANE buffers, so "overlap" lanes never wait on
+// each other's block.  Round 6 measured 12 and 16 lanes: 1/8 shares equal or slower (C2 0.0384-0.0388 ms/frame at 8,
+// 0.0394-0.0420 at 12, 0.0385-0.0392 at 16; C4 0.0465-0.0472 at 8, 0.0483-0.0499 at 16), the whole frame equal at 6
+// and 8 (profiles/r06/lanes/)
+constexpr int NLANE = 8;
+
+// One overlap lane.  Option "overlap" = L lanes: consecutive frames cycle through L lanes (queue heads, unit costs,
+// schedule), so frame k+1's persistent launch fills the CUs frame k's tail leaves idle when the caller cycles L
+// streams; with L <= 1 every frame uses lane 0 and launches of one scene are serialised.  Launches of one lane never
+// overlap, whatever streams callers pass.  The lane's block of the device counters is rt_scene::lane_counters(q).
+struct Lane {
+    // "overlap" frames rendered without a caller stream (opts.stream NULL) run on lane streams the scene owns, created
+    // on first use (frame_stream, render.cpp)
+    hipStream_t st = nullptr;
+    // persistent megakernel: band heads, then (option "reorder") band item counts, one 128 B line each
+    uint32_t *queue = nullptr;
+    hipEvent_t r_done = nullptr;        // last trace launch of the lane finished (FrameBlock::r_used; null: none yet)
+    uint64_t epoch = 0;                 // the counter epoch (rt_scene::cnt_epoch) the lane's counter block belongs to
+    DevBuf<uint32_t> unit_cost, unit_order;   // option "reorder" (schedule.hip)
+    uint32_t sig[7] = {};               // launch layout the recorded costs belong to
+    uint32_t phase = 0;                 // fixed setting "reorder_period" (sched_phase.hpp)
+    bool order_ok = false;              // unit_order holds an order for that layout
+    bool valid = false;                 // sig and the costs are a launch's (not after a build or a change of "reorder")
+    hipError_t create() {               // what survives a rebuild, created once
+        if (queue) return hipSuccess;
+        const hipError_t e = hipMalloc(&queue, QUEUE_WORDS * sizeof(uint32_t));
+        return e == hipSuccess ? hipMemset(queue, 0, QUEUE_WORDS * sizeof(uint32_t)) : e;
+    }
+    void reset() { r_done = nullptr; }  // every launch was seen complete, or given up (abort_comm)
+    void destroy_stream() { if (st) (void)hipStreamDestroy(st); st = nullptr; }   // recreated at the next frame
+    void release() { unit_cost.release(); unit_order.release(); if (queue) (void)hipFree(queue); queue = nullptr; }
+};
+
+// One frame block: per-frame data in HBM (rt_scene::frame_block bytes, laid out by the off_* offsets).
+// r_copied / r_used are what the waits use: the event last recorded for each purpose.  A trace launch records one
+// event after it (its ring_stop timing event, or one event after a multi-GPU gather) and points every purpose
+// it completes at that event (r_copied, r_used, Stage::r_staged, Lane::r_done, rt_scene::r_done) — each event record
+// between two kernels of a stream costs ~5 us of GPU idle time (profiles/r02_gaps.txt), and a launch completed four
+// purposes with four records.
+struct FrameBlock {
+    uint8_t *dev = nullptr;             // HBM
+    hipEvent_t ev_copied = nullptr;     // frame block uploaded / built
+    hipEvent_t ev_used = nullptr;       // last kernel reading dev finished
+    hipEvent_t r_copied = nullptr, r_used = nullptr;   // never null once allocated (reset)
+    hipStream_t chain = nullptr;        // a GPU-built frame's records / TLAS were built on this stream
+    uint32_t items = 0;                 // TLAS items (= instance records when staged by slot)
+    bool by_slot = false;               // staged in slot order
+    hipError_t alloc(size_t bytes) {    // the block anew; the events are created once and survive a rebuild
+        if (dev) { (void)hipFree(dev); dev = nullptr; }
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&dev), bytes);
+        if (e == hipSuccess && !ev_copied) e = hipEventCreateWithFlags(&ev_copied, hipEventDisableTiming);
+        if (e == hipSuccess && !ev_used) e = hipEventCreateWithFlags(&ev_used, hipEventDisableTiming);
+        if (e == hipSuccess && !r_copied) r_copied = ev_copied;
+        if (e == hipSuccess && !r_used) r_used = ev_used;
+        return e;
+    }
+    void reset() { r_copied = ev_copied; r_used = ev_used; }   // the block's own events: no launch to wait for
+    void release() {
+        if (dev) (void)hipFree(dev);
+        if (ev_copied) (void)hipEventDestroy(ev_copied);
+        if (ev_used) (void)hipEventDestroy(ev_used);
+    }
+};
+
+// One pinned host staging buffer of the per-frame upload, allocated on first use (frame_update).
+struct Stage {
+    uint8_t *host = nullptr;
+    uint8_t *dev = nullptr;             // the same, as a device-visible pointer
+    hipEvent_t r_staged = nullptr;      // host no longer read (null: never used, or drained)
+    void reset() { r_staged = nullptr; }
+    void release() { if (host) (void)hipHostFree(host); host = dev = nullptr; r_staged = nullptr; }
+};
+
 // rt_scene_attach_comm: this scene is rank `rank` of a `world`-rank frame.  One communicator
 // per overlap lane at attach time (split from the first), so the lanes' gathers on different streams do not
 // share one; lane q uses comm[q % ncomm] if "overlap" is raised after the attach (every rank issues the same
 // lane sequence, so a shared communicator still sees its operations in one order on every rank).
 struct CommState {
-    static constexpr int NLANE = 8;        // = rt_scene::NLANE
+    static constexpr int NLANE = rtamd::NLANE;
     int rank = 0, world = 1;
     int ncomm = 1;
     uint32_t timeout_ms = 0;               // rt_comm_set_timeout: 0 = no deadline (async errors still polled)
@@ -127,11 +201,7 @@ struct rt_scene {
     std::vector<uint32_t> group_of; // per instance: its group + 1 (0: none)
     bool group_inst = true;         // option "group" (set before the build)
     bool lds_blas = true;           // fixed setting "lds_blas" (an option until round 5): with "lds_scene" 2, a group BLAS's top levels in LDS
-    // frame blocks (= NLANE, below).  Round 6 measured 12 and 16 lanes: 1/8 shares equal or slower (C2 0.0384-0.0388
-    // ms/frame at 8, 0.0394-0.0420 at 12, 0.0385-0.0392 at 16; C4 0.0465-0.0472 at 8, 0.0483-0.0499 at 16), the whole
-    // frame equal at 6 and 8 (profiles/r06/lanes/)
-    static constexpr int NBLOCK = 8;
-    uint32_t frame_items[NBLOCK] = {};   // per frame block: TLAS items (= instance records when staged by slot)
+    static constexpr int NLANE = rtamd::NLANE;   // lanes, and frame blocks: one block per lane
     Tree tlas;
     FlatTree tlas_flat;
     FlatWide tlas_wide;
@@ -149,7 +219,7 @@ struct rt_scene {
         DevBuf<TreeRoot> roots;         // per segment the builder holds (seg_of_blas)
         DevBuf<TriHot> tri_hot; DevBuf<TriCold> tri_cold; DevBuf<SphereHot> sph_hot; DevBuf<PrimCold> sph_cold;
         DevBuf<QuadHot> quad_hot; DevBuf<PrimCold> quad_cold;
-        hipEvent_t ev_lane[NBLOCK] = {};   // one per lane: its last trace of this set
+        hipEvent_t ev_lane[NLANE] = {};    // one per lane: its last trace of this set
         template <typename Self, typename F>
         static void each_buf(Self &b, F f) {
             f(b.pairs); f(b.quads); f(b.roots); f(b.tri_hot); f(b.tri_cold); f(b.sph_hot); f(b.sph_cold); f(b.quad_hot); f(b.quad_cold);
@@ -207,9 +277,7 @@ struct rt_scene {
     // (the root and the item arrays are used by GPU-built TLASes only)
     size_t frame_block = 0, off_root = 0, off_pairs = 0, off_slots = 0, off_hot = 0, off_cold = 0, off_tbox = 0,
            off_tcent = 0, off_root_wide = 0, off_quads = 0, off_delta = 0, off_hot_s = 0, off_cold_s = 0;
-    // frame blocks cycle through NLANE buffers, so "overlap" lanes never wait on each other's block
-    static constexpr int NLANE = 8;
-    static_assert(NLANE == NBLOCK, "one frame block per lane");
+    FrameBlock blk[NLANE];
     // GPU-built frames: per-instance parameters resident in HBM (instances.hip), one copy per frame block
     // (block b's at inst_params.p + b * records), so frames of different lanes update their records
     // concurrently; the host stages a delta (InstDelta at off_delta) only for the records whose transform
@@ -218,7 +286,6 @@ struct rt_scene {
     std::vector<uint16_t> inst_dirty;
     static constexpr uint16_t ALL_BLOCKS = 0xFFFF;
     static_assert(NLANE <= 16, "inst_dirty holds one bit per frame block");
-    hipStream_t chain_stream[NLANE] = {};         // GPU-built frame b's records / TLAS were built on this stream
     hipEvent_t ev_blas_built = nullptr;           // the last GPU BLAS build on the scene stream finished
     hipEvent_t ev_caller = nullptr;               // rt_render with device outputs and no stream: the null stream's
                                                   // work before the call (the trace writes the caller's buffers after it)
@@ -231,21 +298,11 @@ struct rt_scene {
     // option "stage_depth" (default 2 x NLANE): buffers in the cycle, allocated on first use
     static constexpr int NSTAGE = 64;
     int stage_depth = 16;
-    uint8_t *staging[NSTAGE] = {};
-    uint8_t *staging_dev[NSTAGE] = {};            // the same, as device-visible pointers
-    hipEvent_t r_staged[NSTAGE] = {};             // staging[i] no longer read (null: never used)
+    Stage stg[NSTAGE];
     int stage_next = 0;
     int pending_copy = -1, pending_stage = -1;    // rt_render: block (and its staging) whose upload the next launch performs
-    uint8_t *frame_dev[NLANE] = {};               // HBM
-    hipEvent_t ev_copied[NLANE] = {};             // frame block b uploaded / built
-    hipEvent_t ev_used[NLANE] = {};               // last kernel reading frame_dev[b] finished
-    // What the waits below use: the event last recorded for each purpose.  A trace launch records one event
-    // after it (its ring_stop timing event, or one event after a multi-GPU gather) and points every purpose
-    // it completes at that event — each event record between two kernels of a stream costs ~5 us of GPU
-    // idle time (profiles/r02_gaps.txt), and a launch completed four purposes with four records.
-    hipEvent_t r_copied[NLANE] = {}, r_used[NLANE] = {}, r_lane[NLANE] = {};
-    hipEvent_t r_done = nullptr;
-    int active = -1;
+    hipEvent_t r_done = nullptr;                  // last trace launch or query finished (as FrameBlock::r_used; null: none yet)
+    int active = -1;                              // the frame block of the last frame update
     // rt_query_rays: NQUERY slots, taken in turn, of QUERY_PARTS work-queue heads (a 128 B line each) and one completion event.
     // A call's stream first waits on its slot's event — the query that used the slot NQUERY calls ago — so a head is
     // never shared by two queries in flight — and on the previous call's, so queries run in call order.  A frame launch
@@ -266,18 +323,14 @@ struct rt_scene {
     hipEvent_t ring_post[RING] = {};     // multi-GPU frames: the launch's completion event after its gather
     uint32_t ring_head = 0, ring_pending = 0;
     hipStream_t last_stream = nullptr;
-    // persistent megakernel: work-queue head, grid size (#CUs x resident blocks), refill threshold
-    // option "overlap" = L lanes: consecutive frames cycle through L lanes (queue heads, unit costs,
-    // schedule), so frame k+1's persistent launch fills the CUs frame k's tail leaves idle when the caller
-    // cycles L streams; with L <= 1 every frame uses lane 0 and launches of one scene are serialised.
-    uint32_t *queue[NLANE] = {};
-    bool overlap = false;
+    // persistent megakernel: work-queue head (Lane::queue), grid size (#CUs x resident blocks), refill threshold
+    Lane ln[NLANE];
+    bool overlap = false;           // option "overlap": more than one lane in use
     uint32_t blas_leaf = SAH_LEAF_CAP;   // fixed setting "blas_leaf" (an option until round 5): RT_BUILD_SAH BLAS leaf size (1..4), next rt_scene_build
     uint32_t tlas_leaf = 1;   // fixed setting "tlas_leaf" (an option until round 5): RT_BUILD_SAH per-frame SAH TLAS leaf size (1..4; 1 measured best)
     uint32_t tlas_median_leaf = 0;   // fixed setting "tlas_median_leaf" (an option until round 5): RT_BUILD_SAH median TLAS leaf size (0 = the reference's 2)
     bool tlas_sah = true;     // option "tlas_sah": RT_BUILD_SAH builds its per-frame TLAS with SAH (0: the median split)
     bool inst_by_slot = true;       // fixed setting "inst_by_slot" (an option until round 5): host-built TLAS stages instance records in slot order
-    bool block_by_slot[NLANE] = {};  // per frame block: staged in slot order
     uint32_t lanes = 1;
     // fixed setting "reserve" (an option until round 5): with overlapped lanes the persistent grid leaves this many workgroup slots free (two
     // per XCD at 16), so the next lanes' schedule / upload kernels and GPU TLAS builds run beside a launch
@@ -286,10 +339,10 @@ struct rt_scene {
     uint32_t reserve = 16;
     uint32_t lane = 0;              // lane of the next rt_render (overlap)
     int last_lane = 0;              // lane of the last rt_render
-    // "overlap" frames rendered without a caller stream (opts.stream NULL) run on lane streams the scene owns; with
-    // option "overlap" -1 (overlap_auto) the scene also picks the lane count and the staging depth per frame kind
-    // (auto_lanes: the settings bench.py measured best), so a drop-in caller passes no streams at all
-    hipStream_t lane_st[NLANE] = {};
+    // "overlap" frames rendered without a caller stream (opts.stream NULL) run on lane streams the scene owns
+    // (Lane::st); with option "overlap" -1 (overlap_auto) the scene also picks the lane count and the staging depth
+    // per frame kind (auto_lanes: the settings bench.py measured best), so a drop-in caller passes no
+    // streams at all
     bool overlap_auto = false;
     // fixed setting "leaf_early" (an option until round 5) (OutputGPU::leaf_early): -1 = auto, 0 for paths of <= 2 segments (depth x samples; C2, C4),
     // else LEAF_EARLY_AUTO (C3 1.54 -> 1.25, C5 5.79 -> 4.97 ms/frame; C2 0.181 -> 0.185 with it,
@@ -301,7 +354,6 @@ struct rt_scene {
     // 0.180 ms/frame, C3 2.15 -> 1.54, a 1/8 share 0.064 -> 0.046 — as at 12 queues (profiles/r05/lanes/)
     bool lane_priority = true;
     bool stage_depth_set = false;   // option "stage_depth" given explicitly (auto lanes leave it alone)
-    hipEvent_t ev_lane_done[NLANE] = {};   // last trace launch of each lane finished
     uint32_t cus = 0;
     // fixed setting "threshold" (an option until round 5) (lanes waiting before a wave leaves traversal to shade and refill); 0 = auto: 64 when
     // a pixel's path has at most two segments (depth x samples <= 2: the wave then shades and refills all its
@@ -329,14 +381,10 @@ struct rt_scene {
     // heavy-unit pieces: class level for halves | quarters << 8 (0xFF = never); measured (C2 / C3 / C4
     // shares, profiles/r02_sweep_period*.jsonl): quarters from level 12 and no halves
     uint32_t split = 12u | 12u << 8;
-    DevBuf<uint32_t> unit_cost[NLANE], unit_order[NLANE];
-    uint32_t sched_sig[NLANE][7] = {};  // launch layout the recorded costs belong to
     // fixed setting "reorder_period" (an option until round 5) K: a lane records unit costs on one launch in K and rebuilds its order on
     // the next; the launches between reuse the order (the heaviest regions move little between frames)
     uint32_t reorder_period = 8;        // measured: 8 (C2 0.242 ms/step) beats 1 (0.265) with 3 lanes
-    uint32_t sched_phase[NLANE] = {};
-    bool order_ok[NLANE] = {};
-    bool sched_valid[NLANE] = {};
+    void forget_schedules() { for (Lane &l : ln) l.valid = false; }   // every lane's next launch starts a new layout
     DevBuf<uint32_t> costmap;
     size_t costmap_pixels = 0;
     DevBuf<unsigned long long> timeline;
@@ -345,11 +393,11 @@ struct rt_scene {
     // or reading it never races with another lane's launch still in flight (rt_scene_collect sums the lanes)
     unsigned long long *counters = nullptr;       // HBM NLANE x CNT_NUM
     unsigned long long *counters_host = nullptr;  // pinned NLANE x CNT_NUM
+    unsigned long long *lane_counters(int q) const { return counters + (size_t)q * CNT_NUM; }
     // a frame without RT_RENDER_KEEP_COUNTERS starts a new epoch; a lane's block is cleared by the first launch
-    // of that lane in the epoch (no waiting on the other lanes), and rt_scene_collect sums only blocks of the
-    // current epoch
+    // of that lane in the epoch (no waiting on the other lanes: Lane::epoch), and rt_scene_collect sums only blocks
+    // of the current epoch
     uint64_t cnt_epoch = 0;
-    uint64_t lane_epoch[NLANE] = {};
 
     // camera
     bool cam_ok = false;
@@ -413,7 +461,6 @@ struct rt_scene {
     uint32_t blas_sets = 3;
     bool blas_double = true;
     uint64_t blas_builds = 0;
-    hipEvent_t ev_render_done = nullptr;   // last trace launch finished (BLAS rebuilds wait on it)
     bool gpu_tlas_sah = false;          // option "gpu_tlas" (set before the build): RT_BUILD_SAH BLASes, per-frame TLAS on the GPU
     // option "tlas_small": GPU-built frames with at most SMALL_TLAS_MAX records in the TLAS build it in one workgroup
     // (lbvh_tlas_small.hpp tlas_small_kernel) instead of the ~17-launch chain
@@ -521,6 +568,7 @@ rt_status comm_gather(rt_scene *s, int q, uint8_t *frame_out, hipStream_t stream
 // rt_api.cpp, render.cpp
 uint32_t tiles_for_rank(uint32_t w, uint32_t h, uint32_t tw, uint32_t th, uint32_t rank, uint32_t count);
 void fill_stats(rt_stats *st, const unsigned long long *c);
+rt_status sum_lane_counters(rt_scene *s, unsigned long long *sum);
 bool device_accessible(const void *p, int device);
 
 }  // namespace rtamd

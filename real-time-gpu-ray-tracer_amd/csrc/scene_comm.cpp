@@ -19,10 +19,11 @@ void rt_scene::abort_comm() {
         if (comm->comm[q]) (void)rccl().CommAbort(comm->comm[q]);
     delete comm;
     comm = nullptr;
-    for (int q = 0; q < NLANE; q++) r_lane[q] = ev_lane_done[q];
-    r_done = ev_render_done;                   // never recorded after the build's drain: waits on it are no-ops
-    for (int b = 0; b < NLANE; b++) { r_copied[b] = ev_copied[b]; r_used[b] = ev_used[b]; }
-    for (hipEvent_t &e : r_staged) e = nullptr;     // drained: every staging buffer is free
+    // the aborted frames' completion events are given up: nothing waits for them again, every staging buffer is free
+    for (Lane &l : ln) l.reset();
+    r_done = nullptr;
+    for (FrameBlock &b : blk) b.reset();
+    for (Stage &st : stg) st.reset();
 }
 
 namespace rtamd {

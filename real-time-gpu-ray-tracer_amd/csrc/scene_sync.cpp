@@ -14,20 +14,19 @@ rt_scene::~rt_scene() {
     if (comm) {                            // a peer may be gone: bounded waits, abort instead of hanging
         bool ok = true;
         for (int q = 0; q < NLANE && ok; q++)
-            if (r_lane[q]) ok = poll_wait([&] { return query_result(hipEventQuery(r_lane[q])); }, [] { return 0; },
-                                          comm->timeout_ms ? comm->timeout_ms : 10000u) == WaitResult::done;
+            if (ln[q].r_done) ok = poll_wait([&] { return query_result(hipEventQuery(ln[q].r_done)); }, [] { return 0; },
+                                             comm->timeout_ms ? comm->timeout_ms : 10000u) == WaitResult::done;
         if (!ok) abort_comm();
     }
     if (stream) (void)hipStreamSynchronize(stream);
-    for (int q = 0; q < NLANE; q++)          // launches still running on caller streams
-        if (r_lane[q]) (void)hipEventSynchronize(r_lane[q]);
+    for (const Lane &l : ln)                 // launches still running on caller streams
+        if (l.r_done) (void)hipEventSynchronize(l.r_done);
     if (r_done) (void)hipEventSynchronize(r_done);
     for (hipEvent_t e : ev_query)            // ray queries still running on caller streams
         if (e) (void)hipEventSynchronize(e);
     release_comm();
     materials.release(); out_rgba.release(); out_rgb.release();
     timeline.release(); costmap.release();
-    for (int q = 0; q < NLANE; q++) { unit_cost[q].release(); unit_order[q].release(); }
     delete blas_builder; delete tlas_builder;
     raw_tris.release(); raw_verts.release(); raw_sph.release(); raw_quad.release(); inst_blas.release();
     blas_wide_refs.release();
@@ -42,27 +41,18 @@ rt_scene::~rt_scene() {
     };
     drop(cur);
     for (BlasSet &sp : spare) drop(sp);
-    if (ev_render_done) (void)hipEventDestroy(ev_render_done);
     if (ev_caller) (void)hipEventDestroy(ev_caller);
     if (ev_blas_built) (void)hipEventDestroy(ev_blas_built);
     if (ev_raw_staged) (void)hipEventDestroy(ev_raw_staged);
     if (ev_tri_update) (void)hipEventDestroy(ev_tri_update);
     if (raw_stage) (void)hipHostFree(raw_stage);
-    for (int i = 0; i < NSTAGE; i++)
-        if (staging[i]) (void)hipHostFree(staging[i]);
-    for (int b = 0; b < NLANE; b++) {
-        if (frame_dev[b]) (void)hipFree(frame_dev[b]);
-        if (ev_copied[b]) (void)hipEventDestroy(ev_copied[b]);
-        if (ev_used[b]) (void)hipEventDestroy(ev_used[b]);
-    }
+    for (Stage &st : stg) st.release();
+    for (FrameBlock &b : blk) b.release();
     if (counters) (void)hipFree(counters);
     if (query_heads) (void)hipFree(query_heads);
     for (hipEvent_t e : ev_query)
         if (e) (void)hipEventDestroy(e);
-    for (int q = 0; q < NLANE; q++) {
-        if (queue[q]) (void)hipFree(queue[q]);
-        if (ev_lane_done[q]) (void)hipEventDestroy(ev_lane_done[q]);
-    }
+    for (Lane &l : ln) l.release();          // queue heads, unit costs and orders
     if (counters_host) (void)hipHostFree(counters_host);
     for (uint32_t i = 0; i < RING; i++) {
         if (ring_start[i]) (void)hipEventDestroy(ring_start[i]);
@@ -70,8 +60,7 @@ rt_scene::~rt_scene() {
         if (ring_post[i]) (void)hipEventDestroy(ring_post[i]);
     }
     if (stream) (void)hipStreamDestroy(stream);
-    for (hipStream_t &l : lane_st)
-        if (l) (void)hipStreamDestroy(l);
+    for (Lane &l : ln) l.destroy_stream();
 }
 
 namespace rtamd {
@@ -119,8 +108,8 @@ rt_status wait_event(rt_scene *s, hipEvent_t ev) {
 rt_status drain(rt_scene *s) {
     if (s->last_stream) RT_TRY(wait_stream(s, s->last_stream));
     if (s->stream) RT_TRY(wait_stream(s, s->stream));
-    for (int q = 0; q < rt_scene::NLANE; q++)
-        if (s->r_lane[q]) RT_TRY(wait_event(s, s->r_lane[q]));
+    for (const Lane &l : s->ln)
+        if (l.r_done) RT_TRY(wait_event(s, l.r_done));
     if (s->r_done) RT_TRY(wait_event(s, s->r_done));
     if (s->query_live) {                                  // ray queries on caller streams
         for (hipEvent_t e : s->ev_query)
@@ -167,14 +156,14 @@ rt_status wait_blas_built(rt_scene *s, hipStream_t st) {
 }
 
 // Order stream `st` after the record chains (instance update + TLAS build: microseconds, not the traces) of the GPU-built
-// frames already enqueued on other streams: ev_copied[b] is recorded behind block b's chain.  What rewrites data every
+// frames already enqueued on other streams: a block's ev_copied is recorded behind its chain.  What rewrites data every
 // block's chain reads — the device-bounded centroids (RT_TRI_UPDATE_BOUNDS) — waits for them; a chain that has
 // finished needs no wait (a host query).
 rt_status wait_record_chains(rt_scene *s, hipStream_t st) {
-    for (int b = 0; b < rt_scene::NLANE; b++) {
-        if (!s->chain_stream[b] || s->chain_stream[b] == st || !s->ev_copied[b]) continue;
+    for (const FrameBlock &b : s->blk) {
+        if (!b.chain || b.chain == st || !b.ev_copied) continue;
         bool pending;
-        RT_TRY(wait_if_pending(st, s->ev_copied[b], &pending));
+        RT_TRY(wait_if_pending(st, b.ev_copied, &pending));
     }
     return RT_OK;
 }
@@ -197,7 +186,7 @@ rt_status order_after_stream(rt_scene *s, hipStream_t from, hipStream_t st) {
 // bounded polls when one is attached (never a device-wide synchronisation).
 rt_status wait_frame_block(rt_scene *s) {
     RT_TRY(drain(s));
-    if (s->active >= 0 && s->r_copied[s->active]) RT_TRY(wait_event(s, s->r_copied[s->active]));
+    if (s->active >= 0 && s->blk[s->active].r_copied) RT_TRY(wait_event(s, s->blk[s->active].r_copied));
     return RT_OK;
 }
 

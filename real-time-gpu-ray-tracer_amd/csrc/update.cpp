@@ -115,8 +115,8 @@ rt_status tri_update_check(const rt_scene *s, uint64_t first, uint64_t count) {
 rt_status tri_update_waits(rt_scene *s) {
     if (!s->raw_shading()) return RT_OK;
     if (s->r_done) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_done, 0));
-    for (int q = 0; q < rt_scene::NLANE; q++)
-        if (s->r_lane[q]) HIP_TRY(hipStreamWaitEvent(s->stream, s->r_lane[q], 0));
+    for (const Lane &l : s->ln)
+        if (l.r_done) HIP_TRY(hipStreamWaitEvent(s->stream, l.r_done, 0));
     return wait_queries(s, s->stream);               // a query's records read raw_tris too (finalize, RAW 1)
 }
 
