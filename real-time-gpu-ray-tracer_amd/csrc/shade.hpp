@@ -71,7 +71,7 @@ __device__ __forceinline__ Surface finalize(const SceneGPU &sc, const f3 &wo, co
         s.material = C.material; s.orig = C.orig_index; s.member = 0u;
     } else {                                                                   // Parallelogram.cu:42-43
 #if !RT_EXACT
-        const float4 qn4 = LDSS && sc.lds_q_hot != LDS_NONE ? lds_scene[sc.lds_q_hot + h.slot * LDS_QPRIM_F4]
+        const float4 qn4 = LDSS && sc.lds_q_hot != LDS_NONE ? lds_scene[sc.lds_q_hot + times<LDS_QPRIM_F4>(h.slot)]
                                                               : reinterpret_cast<const float4 *>(sc.quad_hot + h.slot)[0];
         const PrimCold C = LDSS ? lds_or_global(sc.lds_q_cold, sc.quad_cold, h.slot) : sc.quad_cold[h.slot];
         const f3 qn = mk(qn4.x, qn4.y, qn4.z);

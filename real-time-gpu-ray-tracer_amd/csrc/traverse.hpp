@@ -217,6 +217,23 @@ __device__ __forceinline__ void postpone_leaf(Trav &T, const SEnt *spill) {
     pop_next<XB>(T, spill);
 }
 
+// k * N for a record of N dwordx4 (N <= 8) as shifts and adds, ahead of a dependent load: v_mul_lo_u32 and
+// v_mad_u64_u32 issue at a quarter of the rate.  The optimiser folds a plain (k << 3) - k back into the multiply, so
+// the shifted value passes through an empty asm.
+template <uint32_t N>
+__device__ __forceinline__ uint32_t times(uint32_t k) {
+    static_assert(N >= 1 && N <= 8, "a small record size");
+    if constexpr ((N & (N - 1)) == 0) {
+        return k * N;
+    } else if constexpr (N == 6) {
+        return times<3>(k) << 1;
+    } else {
+        uint32_t s = k << (N == 3 ? 1 : (N == 5 ? 2 : 3));
+        asm("" : "+v"(s));
+        return N == 7 ? s - k : s + k;
+    }
+}
+
 // One interior-loop step of a lane whose cur is an interior node.
 #if !RT_EXACT
 // Quad node (option "wide", layout.hpp NodeQuad): 4 slab tests on SoA bounds; the hit slots are visited
@@ -236,10 +253,11 @@ template <bool LDSS>
 __device__ __forceinline__ InstRec load_inst(const SceneGPU &sc, uint32_t i) {
     InstRec r;
     if (LDSS && sc.lds_insts) {
-        const float4 *p = lds_scene + sc.lds_quads * LDS_QUAD_F4 + i * LDS_INST_F4;
+        const float4 *p = lds_scene + sc.lds_quads * LDS_QUAD_F4 + times<LDS_INST_F4>(i);
         r.i0 = p[0]; r.i1 = p[1]; r.i2 = p[2]; r.box01 = p[3]; r.box2ref = p[4];
     } else {
-        const float4 *p = reinterpret_cast<const float4 *>(sc.inst_hot + i);
+        static_assert(sizeof(InstHot) == LDS_INST_F4 * 16, "InstHot is LDS_INST_F4 dwordx4");
+        const float4 *p = reinterpret_cast<const float4 *>(sc.inst_hot) + times<LDS_INST_F4>(i);     // (i < 2^26)
         r.i0 = p[0]; r.i1 = p[1]; r.i2 = p[2]; r.box01 = p[3]; r.box2ref = p[4];
     }
     return r;
@@ -278,9 +296,9 @@ __device__ __forceinline__ R lds_or_global(uint32_t at, const R *g, uint32_t k) 
     float4 *d = reinterpret_cast<float4 *>(&r);
     if (at != LDS_NONE) {
 #pragma unroll
-        for (uint32_t j = 0; j < N4; j++) d[j] = lds_scene[at + k * N4 + j];
+        for (uint32_t j = 0; j < N4; j++) d[j] = lds_scene[at + times<N4>(k) + j];
     } else {
-        const float4 *p = reinterpret_cast<const float4 *>(g + k);
+        const float4 *p = reinterpret_cast<const float4 *>(g) + times<N4>(k);     // (k < 2^26: an instance or a slot)
 #pragma unroll
         for (uint32_t j = 0; j < N4; j++) d[j] = p[j];
     }
@@ -300,14 +318,17 @@ __device__ __forceinline__ void wide_interior_step(Trav &T, const SceneGPU &sc, 
     const bool blas = (cur & REF_BLAS) != 0;
     float4 lx, hx, ly, hy, lz, hz;
     uint4 R;
-    // one code path: a generic pointer into the LDS scene region or HBM (flat loads serve both)
+    // one code path: a generic pointer into the LDS scene region or HBM (flat loads serve both), chosen once as a
+    // base and a byte offset (an LDS record is LDS_QUAD_F4 dwordx4 and its index small; a NodeQuad in HBM is 128 B)
     const float4 *Q;
     {
         const uint32_t qi = cur & REF_INDEX_MASK, qb = qi - sc.lds_bq0;
         const bool in_lds = blas ? qb < sc.lds_bqn : sc.lds_quads != 0;
-        const uint32_t at = blas ? sc.lds_bq_at + qb * LDS_QUAD_F4 : qi * LDS_QUAD_F4;
-        Q = in_lds ? static_cast<const float4 *>(lds_scene + at)
-                   : reinterpret_cast<const float4 *>((blas ? sc.blas_quads : sc.tlas_quads) + qi);
+        const uint32_t at = (blas ? sc.lds_bq_at : 0u) + times<LDS_QUAD_F4>(blas ? qb : qi);
+        const char *base = in_lds ? reinterpret_cast<const char *>(static_cast<const float4 *>(lds_scene))
+                                  : reinterpret_cast<const char *>(blas ? sc.blas_quads : sc.tlas_quads);
+        const uint64_t off = in_lds ? (uint64_t)(at << 4) : (uint64_t)qi << 7;
+        Q = reinterpret_cast<const float4 *>(base + off);
         lx = Q[0]; hx = Q[1]; ly = Q[2]; hy = Q[3]; lz = Q[4]; hz = Q[5];
         R = reinterpret_cast<const uint4 *>(Q)[6];
     }
@@ -468,7 +489,9 @@ __device__ __forceinline__ uint32_t spec_leaf_phase(Trav &T, const SceneGPU &sc,
                 // `k0 + k < count` would be issued only after the previous triangles' loads were waited for
 #pragma unroll
                 for (uint32_t k = 0; k < TRI_AHEAD; k++) {
-                    const float *src = sc.tri_hot[start + min(k0 + k, count - 1u)].v0;
+                    static_assert(sizeof(TriHot) == 48 && offsetof(TriHot, v0) == 0, "TriHot is 3 dwordx4, v0 first");
+                    const float *src = reinterpret_cast<const float *>(sc.tri_hot) +
+                                       (times<3>(start + min(k0 + k, count - 1u)) << 2);   // (slot < 2^26)
                     const float3 a = *reinterpret_cast<const float3 *>(src);
                     const float3 b = *reinterpret_cast<const float3 *>(src + 4);
                     const float3 c = *reinterpret_cast<const float3 *>(src + 8);
@@ -551,11 +574,17 @@ template <bool COUNT, int WIDE = 0>
 __device__ __forceinline__ void spec_round(Trav &T, const SceneGPU &sc, SEnt *spill, LaneCount &cnt,
                                            PhaseCycles &pc, uint32_t &steps, bool track, uint32_t leaf_early) {
     DIAG_T(t0);
-    for (;;) {
+    // The loop's exit tests stand ahead of the loop and at the end of its body, not in the middle of `for (;;)`: with
+    // the breaks inside, the compiler carries the lane's state (cur, curT, the stack's top and counts) through the body
+    // in a second set of registers and moves it back every iteration (about 14 v_mov_b32 per iteration of the
+    // benched instantiation); with the tests at the end it updates the state in place.
+    const auto more = [&]() -> bool {
         if (T.tracing && T.pleaf == REF_NONE && T.cur == REF_NONE) T.tracing = false;   // done, no leaf left
         const uint64_t looking = __ballot(T.tracing && T.pleaf == REF_NONE);
-        if (!looking) break;
-        if (leaf_early && (uint32_t)__popcll(looking) <= leaf_early && __any(T.tracing && T.pleaf != REF_NONE)) break;
+        if (!looking) return false;
+        return !(leaf_early && (uint32_t)__popcll(looking) <= leaf_early && __any(T.tracing && T.pleaf != REF_NONE));
+    };
+    for (bool go = more(); go; go = more()) {
         const bool active = T.tracing && T.cur != REF_NONE && (!(T.cur & REF_LEAF) || T.pleaf == REF_NONE);
         const bool node = active && !(T.cur & REF_LEAF);
         if (RT_DIAG) {
