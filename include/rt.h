@@ -33,7 +33,8 @@ extern "C" {
  * 3: rt_scene_info gained overlap_lanes / stage_depth; "overlap" -1 = library-picked lanes on library streams
  * 4: rt_query_rays
  * 5: rt_scene_update_triangles_device
- *    (RT_TRI_UPDATE_BOUNDS arrived within 5: a flag value that was rejected before is accepted now) */
+ *    (RT_TRI_UPDATE_BOUNDS arrived within 5: a flag value that was rejected before is accepted now;
+ *     rt_query_camera / rt_camera_query arrived within 5: a new entry point, no existing struct changed) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -389,6 +390,59 @@ typedef struct rt_ray_query {
 } rt_ray_query;
 
 rt_status rt_query_rays(rt_scene *scene, const rt_ray_query *query);
+
+/* Camera ray queries: per pixel of a rectangle of the current camera frame, the camera's own ray, its closest hit and
+ * the hit material's albedo, all on the device.  The ray is built in registers by the query kernel from the camera the
+ * scene holds (csrc/ray_query.hpp): no ray buffer is written unless rays_device asks for one.
+ *
+ * Outputs  : each optional, at least one; row-major over the rectangle — pixel (x0 + i, y0 + j) is element
+ *            j * width + i; row 0 is the bottom row, as in the framebuffer.
+ * Rays     : evaluated without FMA contraction and with correctly rounded 1 / sqrt in all three flavours (option
+ *            "fast_math" included, whose render kernels may start a path one rounding away from it).
+ *            Default (pixel centre): origin = the camera's centre, direction = unit((pixel_origin + dx * (float)px +
+ *            dy * (float)py) - centre) in the render kernels' operation order with the sample offset 0: no RNG and no
+ *            focus disk, whatever the camera's sample_count and focus_disk_radius.  The picking and depth ray; it
+ *            depends on no seed.
+ *            RT_CAMERA_QUERY_FIRST_SAMPLE: the ray rt_render starts the pixel's first path with for frame_seed (0 ->
+ *            0x5EED, as rt_render_opts.frame_seed): the pixel's RNG stream (keyed by the padded pitch), the jitter
+ *            inside sample cell (0, 0) of the sqrt(sample_count) grid, and the focus disk when its radius is > 0.
+ *            Only sample 0 is offered: a later sample's ray depends on the RNG values the pixel's earlier paths
+ *            consumed, which only rendering them yields.
+ * Trace    : closest hit over [0.001, +inf), the renderer's range, on the scene as of the last frame update and the
+ *            camera as of this call (rt_camera_set).  hits_device[k] and t_device[k] are byte for byte what
+ *            rt_query_rays writes for rays_device[k] with tmax_device NULL and the same EXACT flag.  albedo_device: the
+ *            albedo of the hit's material slot, rough or metal; on a miss the camera's background (what multiplies
+ *            the path there, and the usual convention for a denoiser's albedo guide).  With rays_device as the only
+ *            output nothing is traversed.
+ * Flags    : RT_CAMERA_QUERY_EXACT / RT_CAMERA_QUERY_NO_SYNC as RT_QUERY_EXACT / RT_QUERY_NO_SYNC.
+ * Ordering : rt_query_rays' rules: `stream`, the null-stream behaviour, what the launch waits for, what waits for it,
+ *            rt_synchronize and rt_scene_destroy.  Camera queries and ray queries of one scene share one sequence and
+ *            run in the order of their calls.
+ * Errors   : all before anything is enqueued.  RT_ERR_INVALID_ARGUMENT for a NULL scene or query, reserved != 0,
+ *            unknown flags, no output buffer, a rectangle not inside the camera's frame (x0 + width and y0 + height
+ *            checked without overflow), or a buffer that hipPointerGetAttributes does not report as accessible from
+ *            the scene's device; RT_ERR_STATE before rt_scene_build, before the first rt_camera_set, and after a
+ *            triangle update until a frame has run its update.  width * height == 0 returns RT_OK and launches
+ *            nothing.  The caller's current device is preserved.  Allowed while a communicator is attached. */
+typedef enum rt_camera_query_flags {
+    RT_CAMERA_QUERY_EXACT        = 1u << 0,  /* as RT_QUERY_EXACT */
+    RT_CAMERA_QUERY_NO_SYNC      = 1u << 2,  /* as RT_QUERY_NO_SYNC (same bit) */
+    RT_CAMERA_QUERY_FIRST_SAMPLE = 1u << 3   /* the frame's own first camera ray */
+} rt_camera_query_flags;
+
+typedef struct rt_camera_query {
+    uint32_t x0, y0, width, height; /* pixel rectangle of the current camera frame; row 0 = bottom, as the framebuffer */
+    uint64_t frame_seed;            /* FIRST_SAMPLE only: as rt_render_opts.frame_seed (0 -> 0x5EED) */
+    uint32_t flags;
+    uint32_t reserved;              /* 0 */
+    float  *rays_device;            /* optional, 6 floats per pixel: origin xyz, direction xyz */
+    float  *t_device;               /* optional, 1 float per pixel: +inf on a miss */
+    rt_hit *hits_device;            /* optional: exactly the record rt_query_rays writes for that ray */
+    float  *albedo_device;          /* optional, 3 floats per pixel: the hit material's albedo; the camera's background on a miss */
+    void   *stream;                 /* as rt_ray_query.stream */
+} rt_camera_query;                  /* 72 bytes on LP64 */
+
+rt_status rt_query_camera(rt_scene *scene, const rt_camera_query *query);
 
 /* The box decisions of the trace kernels on caller data, for parity tests (no scene needed): box i =
  * {xmin, xmax, ymin, ymax, zmin, zmax} (6 floats), ray i = origin xyz, direction xyz, range [0.001, tmax[i]].

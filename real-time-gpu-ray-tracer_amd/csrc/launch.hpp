@@ -21,7 +21,9 @@ namespace rtamd {
                                               unsigned long long *, uint32_t *, uint32_t, uint32_t, bool, hipStream_t);  \
     uint32_t persistent_blocks_per_cu_##sfx(uint32_t wide, bool raw);                                                     \
     hipError_t launch_trace_rays_##sfx(const SceneGPU &, const float *, uint32_t, rt_hit *, hipStream_t);                \
-    hipError_t launch_ray_query_##sfx(const SceneGPU &, const RayQueryGPU &, bool, uint32_t, hipStream_t);
+    hipError_t launch_ray_query_##sfx(const SceneGPU &, const RayQueryGPU &, bool, uint32_t, hipStream_t);               \
+    hipError_t launch_camera_query_##sfx(const SceneGPU &, const CameraGPU &, RayQueryGPU, CameraQueryGPU, uint32_t,     \
+                                         hipStream_t);
 RTAMD_TRACE_LAUNCHERS(exact)
 RTAMD_TRACE_LAUNCHERS(fast)
 RTAMD_TRACE_LAUNCHERS(fastmath)
@@ -66,11 +68,12 @@ struct TraceFlavour {
     decltype(&persistent_blocks_per_cu_exact) blocks_per_cu;
     decltype(&launch_trace_rays_exact) trace_rays;
     decltype(&launch_ray_query_exact) ray_query;
+    decltype(&launch_camera_query_exact) camera_query;
 };
 inline const TraceFlavour &trace_flavour(bool exact, bool fast_math) {
 #define RTAMD_FLAVOUR(sfx)                                                                                                \
     {launch_render_##sfx, launch_render_persistent_##sfx, persistent_blocks_per_cu_##sfx, launch_trace_rays_##sfx,       \
-     launch_ray_query_##sfx}
+     launch_ray_query_##sfx, launch_camera_query_##sfx}
     static constexpr TraceFlavour table[3] = {RTAMD_FLAVOUR(exact), RTAMD_FLAVOUR(fast), RTAMD_FLAVOUR(fastmath)};
 #undef RTAMD_FLAVOUR
     return table[exact ? 0 : (fast_math ? 2 : 1)];

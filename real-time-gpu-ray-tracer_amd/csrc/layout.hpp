@@ -272,6 +272,17 @@ struct RayQueryGPU {
     uint32_t *head;                 // QUERY_PARTS band heads, QUEUE_STRIDE words apart: chunks of 64 rays claimed so
                                     // far in each band (zeroed before the launch)
 };
+// rt_query_camera (ray_query.hpp): the query kernel's second ray source.  The work items are the pixels of a rectangle
+// of the camera's frame in row-major order, 64 per claimed chunk.  RayQueryGPU carries the item count (n = w h), t,
+// hits and the heads; CameraGPU the camera and, in frame_seed, the seed of the first-sample rays.
+struct CameraQueryGPU {
+    uint32_t x0, y0, w, h;          // the rectangle; output element of pixel (x0 + i, y0 + j): j * w + i
+    uint32_t blocks_x;              // ceil(w / 8): the 8x8-block claim variant (RT_CAMERA_QUERY_BLOCKS)
+    uint32_t first_sample;          // 0: the ray through the pixel's centre; 1: the frame's first sample of the pixel
+    uint32_t trace;                 // 0: rays only, nothing is traversed
+    float *rays;                    // optional: 6 floats per pixel
+    float *albedo;                  // optional: 3 floats per pixel
+};
 constexpr uint32_t QUERY_PARTS = 8;           // bands of a query's chunks, one per XCD (as the frame's queue_parts)
 constexpr uint32_t QUEUE_STRIDE = 32;         // u32 words between partition heads (128 B lines)
 constexpr uint32_t QUEUE_MAX_PARTS = 8;

@@ -382,6 +382,51 @@ bool device_accessible(const void *p, int device) {
 
 }  // namespace rtamd
 
+namespace {
+
+// rt_query_rays and rt_query_camera from the validated call on (the scene's device is current): the dependency waits,
+// the launch — launch(scene, the slot's band heads, stream) -> hipError_t — and the bookkeeping of one query.
+template <class Launch>
+rt_status enqueue_query(rt_scene *s, void *caller_stream, bool no_sync, Launch &&launch) {
+    hipStream_t st = caller_stream ? static_cast<hipStream_t>(caller_stream) : s->stream;
+    const uint32_t slot = s->query_next;       // advanced once the query is enqueued: a failed call takes no slot
+    hipEvent_t done = s->ev_query[slot];
+    FrameBlock &blk = s->blk[s->active];
+    // What the launch waits for.  Its slot's previous query (head free; see ev_query) and the previous call's (queries
+    // run in call order even with a frame's launch between them).  The frame block of the last
+    // update, as a RT_RENDER_SKIP_UPDATE frame does, and a GPU BLAS build still running on the scene's stream.  And
+    // every event this call replaces below — the block's r_used, r_done, the BLAS set's reader event: whoever waits on those
+    // afterwards sees only this query, which runs on a caller stream and so implies nothing about the launches on the
+    // lane streams they stood for.
+    // An event that has already completed needs no wait (a host query, ~1 us, as wait_blas_built): whatever is enqueued
+    // now runs after it, and each cross-stream wait in front of a kernel costs GPU idle time (DESIGN.md §4).  The
+    // purposes often share one event (a frame's single completion event): each is waited on once.
+    const int bl = s->last_lane;
+    hipEvent_t prev_query = s->ev_query[(slot + rt_scene::NQUERY - 1) % rt_scene::NQUERY];
+    hipEvent_t deps[] = {done, prev_query, blk.r_copied, blk.r_used, s->r_done, s->cur.ev_lane[bl]};
+    for (size_t i = 0; i < sizeof deps / sizeof deps[0]; i++) {
+        bool dup = !deps[i];
+        for (size_t j = 0; j < i && !dup; j++) dup = deps[j] == deps[i];
+        bool pending;
+        if (!dup) RT_TRY(wait_if_pending(st, deps[i], &pending));
+    }
+    // the caller's null-stream work (rt_render)
+    if (!caller_stream && hipStreamQuery(nullptr) == hipErrorNotReady) RT_TRY(order_after_null_stream(s, st));
+    if (s->blas_build_seq != 0 && st != s->stream) RT_TRY(wait_blas_built(s, st));
+
+    HIP_TRY(launch(scene_gpu(s), s->query_heads + (size_t)slot * QUERY_PARTS * QUEUE_STRIDE, st));
+    HIP_TRY(hipEventRecord(done, st));
+    s->query_next = (slot + 1) % rt_scene::NQUERY;
+    s->query_live = true;
+    blk.r_used = s->r_done = done;             // later uploads into the block, later BLAS rebuilds, rt_synchronize
+    if (s->cur.ev_lane[bl]) HIP_TRY(hipEventRecord(s->cur.ev_lane[bl], st));   // "blas_double": this set's reader
+    if (!caller_stream) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
+    if (no_sync) return RT_OK;
+    return wait_event(s, done);
+}
+
+}  // namespace
+
 extern "C" {
 
 rt_status rt_render(rt_scene *s, uint64_t frame, const rt_render_opts *opts, uint8_t *rgba_host, float *rgb_host,
@@ -528,47 +573,56 @@ rt_status rt_query_rays(rt_scene *s, const rt_ray_query *qy) {
         if (p && !device_accessible(p, s->device))
             return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_rays: a buffer is not accessible from the scene's device");
 
-    hipStream_t st = qy->stream ? static_cast<hipStream_t>(qy->stream) : s->stream;
-    const uint32_t slot = s->query_next;       // advanced once the query is enqueued: a failed call takes no slot
-    hipEvent_t done = s->ev_query[slot];
-    FrameBlock &blk = s->blk[s->active];
-    // What the launch waits for.  Its slot's previous query (head free; see ev_query) and the previous call's (queries
-    // run in call order even with a frame's launch between them).  The frame block of the last
-    // update, as a RT_RENDER_SKIP_UPDATE frame does, and a GPU BLAS build still running on the scene's stream.  And
-    // every event this call replaces below — the block's r_used, r_done, the BLAS set's reader event: whoever waits on those
-    // afterwards sees only this query, which runs on a caller stream and so implies nothing about the launches on the
-    // lane streams they stood for.
-    // An event that has already completed needs no wait (a host query, ~1 us, as wait_blas_built): whatever is enqueued
-    // now runs after it, and each cross-stream wait in front of a kernel costs GPU idle time (DESIGN.md §4).  The
-    // purposes often share one event (a frame's single completion event): each is waited on once.
-    const int bl = s->last_lane;
-    hipEvent_t prev_query = s->ev_query[(slot + rt_scene::NQUERY - 1) % rt_scene::NQUERY];
-    hipEvent_t deps[] = {done, prev_query, blk.r_copied, blk.r_used, s->r_done, s->cur.ev_lane[bl]};
-    for (size_t i = 0; i < sizeof deps / sizeof deps[0]; i++) {
-        bool dup = !deps[i];
-        for (size_t j = 0; j < i && !dup; j++) dup = deps[j] == deps[i];
-        bool pending;
-        if (!dup) RT_TRY(wait_if_pending(st, deps[i], &pending));
-    }
-    // the caller's null-stream work (rt_render)
-    if (!qy->stream && hipStreamQuery(nullptr) == hipErrorNotReady) RT_TRY(order_after_null_stream(s, st));
-    if (s->blas_build_seq != 0 && st != s->stream) RT_TRY(wait_blas_built(s, st));
-
-    const SceneGPU g = scene_gpu(s);
     RayQueryGPU q{};
     q.rays = qy->rays_device; q.tmax = qy->tmax_device;
     q.n = (uint32_t)qy->ray_count;
     q.hits = qy->hits_device; q.t = qy->t_device; q.occluded = qy->occluded_device;
-    q.head = s->query_heads + (size_t)slot * QUERY_PARTS * QUEUE_STRIDE;
-    HIP_TRY(trace_flavour((qy->flags & RT_QUERY_EXACT) != 0, s->fast_math).ray_query(g, q, any, s->cus, st));
-    HIP_TRY(hipEventRecord(done, st));
-    s->query_next = (slot + 1) % rt_scene::NQUERY;
-    s->query_live = true;
-    blk.r_used = s->r_done = done;             // later uploads into the block, later BLAS rebuilds, rt_synchronize
-    if (s->cur.ev_lane[bl]) HIP_TRY(hipEventRecord(s->cur.ev_lane[bl], st));   // "blas_double": this set's reader
-    if (!qy->stream) HIP_TRY(hipStreamWaitEvent(nullptr, done, 0));
-    if (qy->flags & RT_QUERY_NO_SYNC) return RT_OK;
-    return wait_event(s, done);
+    const TraceFlavour &fl = trace_flavour((qy->flags & RT_QUERY_EXACT) != 0, s->fast_math);
+    return enqueue_query(s, qy->stream, (qy->flags & RT_QUERY_NO_SYNC) != 0,
+                         [&](const SceneGPU &g, uint32_t *head, hipStream_t st) {
+                             q.head = head;
+                             return fl.ray_query(g, q, any, s->cus, st);
+                         });
+}
+
+rt_status rt_query_camera(rt_scene *s, const rt_camera_query *cq) {
+    if (!s || !cq) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    const uint32_t known = RT_CAMERA_QUERY_EXACT | RT_CAMERA_QUERY_NO_SYNC | RT_CAMERA_QUERY_FIRST_SAMPLE;
+    if (cq->reserved != 0 || (cq->flags & ~known)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_camera: reserved bits set");
+    if (!cq->rays_device && !cq->t_device && !cq->hits_device && !cq->albedo_device)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_camera: no output buffer");
+    if (!s->built) return fail(RT_ERR_STATE, "rt_scene_build has not been called");
+    if (!s->cam_ok) return fail(RT_ERR_STATE, "rt_camera_set has not been called");
+    // the rectangle inside the frame, without forming x0 + width
+    if (cq->x0 > s->width || cq->width > s->width - cq->x0 || cq->y0 > s->height || cq->height > s->height - cq->y0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_camera: the rectangle is not inside the camera's frame");
+    // work items (the pixels; 64 per 8x8 block in the block-claim variant) and output elements are 32-bit indices
+    const uint64_t blocks = (uint64_t)((cq->width + 7u) / 8u) * ((cq->height + 7u) / 8u);
+    if (blocks * 64u > 0xFFFFFFFFull) return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_camera: too many pixels");
+    if (cq->width == 0 || cq->height == 0) return RT_OK;
+    if (s->blas_dirty) return fail_blas_dirty();
+    DeviceRestore restore;
+    HIP_TRY(hipSetDevice(s->device));
+    const void *bufs[] = {cq->rays_device, cq->t_device, cq->hits_device, cq->albedo_device};
+    for (const void *p : bufs)
+        if (p && !device_accessible(p, s->device))
+            return fail(RT_ERR_INVALID_ARGUMENT, "rt_query_camera: a buffer is not accessible from the scene's device");
+
+    RayQueryGPU q{};
+    q.hits = cq->hits_device; q.t = cq->t_device;
+    CameraQueryGPU c{};
+    c.x0 = cq->x0; c.y0 = cq->y0; c.w = cq->width; c.h = cq->height;
+    c.first_sample = (cq->flags & RT_CAMERA_QUERY_FIRST_SAMPLE) ? 1u : 0u;
+    c.trace = (cq->t_device || cq->hits_device || cq->albedo_device) ? 1u : 0u;
+    c.rays = cq->rays_device; c.albedo = cq->albedo_device;
+    CameraGPU cam = s->cam;                    // the camera as of this call
+    cam.frame_seed = cq->frame_seed ? cq->frame_seed : 0x5EEDull;      // as rt_render_opts.frame_seed
+    const TraceFlavour &fl = trace_flavour((cq->flags & RT_CAMERA_QUERY_EXACT) != 0, s->fast_math);
+    return enqueue_query(s, cq->stream, (cq->flags & RT_CAMERA_QUERY_NO_SYNC) != 0,
+                         [&](const SceneGPU &g, uint32_t *head, hipStream_t st) {
+                             q.head = head;
+                             return fl.camera_query(g, cam, q, c, s->cus, st);
+                         });
 }
 
 rt_status rt_box_test(int device, const float *boxes, const float *rays, const float *tmax, size_t n, uint32_t mode,

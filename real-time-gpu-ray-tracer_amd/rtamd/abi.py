@@ -34,6 +34,10 @@ RT_QUERY_EXACT = 1 << 0
 RT_QUERY_ANY_HIT = 1 << 1
 RT_QUERY_NO_SYNC = 1 << 2
 
+RT_CAMERA_QUERY_EXACT = 1 << 0
+RT_CAMERA_QUERY_NO_SYNC = 1 << 2
+RT_CAMERA_QUERY_FIRST_SAMPLE = 1 << 3
+
 RT_TRI_UPDATE_NO_SYNC = 1 << 0
 RT_TRI_UPDATE_BOUNDS = 1 << 1
 
@@ -133,6 +137,14 @@ class RayQuery(C.Structure):
                 ("t_device", C.c_void_p), ("occluded_device", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class CameraQuery(C.Structure):
+    """rt_camera_query: pixel rectangle, seed, flags, device outputs and stream of one rt_query_camera call."""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("frame_seed", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("rays_device", C.c_void_p), ("t_device", C.c_void_p), ("hits_device", C.c_void_p),
+                ("albedo_device", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class TriangleUpdate(C.Structure):
     """rt_triangle_update: triangle range, device vertex / normal streams and stream of one
     rt_scene_update_triangles_device call."""
@@ -191,7 +203,7 @@ EXPORTED_SYMBOLS = (
     "rt_vtk_series_read", "rt_vtk_series_count", "rt_vtk_series_entry", "rt_vtk_series_free",
     "rt_comm_unique_id", "rt_scene_attach_comm", "rt_scene_detach_comm", "rt_slab_tiles", "rt_tile_pixels",
     "rt_comm_set_timeout", "rt_camera_control_init", "rt_camera_move", "rt_clock_ns", "rt_frame_pace",
-    "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device",
+    "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device", "rt_query_camera",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -221,6 +233,8 @@ def _declare(lib):
     lib.rt_box_test.restype = C.c_int
     lib.rt_query_rays.argtypes = [C.c_void_p, P(RayQuery)]
     lib.rt_query_rays.restype = C.c_int
+    lib.rt_query_camera.argtypes = [C.c_void_p, P(CameraQuery)]
+    lib.rt_query_camera.restype = C.c_int
     lib.rt_synchronize.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.restype = None

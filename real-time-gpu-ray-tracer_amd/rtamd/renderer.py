@@ -335,6 +335,43 @@ class Renderer:
             return occ[:n].view(torch.bool)
         return t[:n], (hits[:n] if want_hits else None)
 
+    def query_camera(self, rect=None, *, first_sample: bool = False, frame_seed: int = 0x5EED, exact: bool = False,
+                     want_rays: bool = False, want_t: bool = True, want_hits: bool = False, want_albedo: bool = False,
+                     stream=None, sync: bool = True):
+        """rt_query_camera: the camera's own rays over rect = (x0, y0, width, height) of the current frame (None: the
+        whole frame; row 0 is the bottom row), traced on the device.  The rays go through the pixel centres, or with
+        first_sample are the rays render() starts each pixel's first path with for frame_seed.  Returns a dict of
+        torch CUDA tensors with the keys asked for: "t" float32 [h, w] (+inf on a miss), "rays" float32 [h, w, 6],
+        "hits" uint8 [h, w, 48] (rt_hit records, see hits_to_numpy) and "albedo" float32 [h, w, 3] (the hit
+        material's albedo, the background on a miss).  stream: a torch.cuda.Stream or a raw hipStream_t (None =
+        torch's current stream); with sync=False the call returns after the enqueue and the tensors are valid in
+        stream order."""
+        import torch                              # here: `import rtamd` needs no torch
+
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+        x0, y0, w, h = (0, 0, self.width, self.height) if rect is None else (int(v) for v in rect)
+        q = abi.CameraQuery()
+        q.x0, q.y0, q.width, q.height = x0, y0, w, h
+        q.frame_seed = frame_seed
+        q.flags = (abi.RT_CAMERA_QUERY_EXACT if exact else 0) | (0 if sync else abi.RT_CAMERA_QUERY_NO_SYNC) | \
+                  (abi.RT_CAMERA_QUERY_FIRST_SAMPLE if first_sample else 0)
+        q.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        out = {}
+        with ctx:                                 # outputs made on the query's stream, as query_rays
+            for want, key, field, tail, dtype in ((want_rays, "rays", "rays_device", (6,), torch.float32),
+                                                  (want_t, "t", "t_device", (), torch.float32),
+                                                  (want_hits, "hits", "hits_device", (C.sizeof(abi.Hit),), torch.uint8),
+                                                  (want_albedo, "albedo", "albedo_device", (3,), torch.float32)):
+                if want:
+                    buf = torch.empty((max(h, 0) * max(w, 0) + 1,) + tail, dtype=dtype, device=dev)
+                    setattr(q, field, buf.data_ptr())
+                    out[key] = buf
+        abi.check(self.lib, self.lib.rt_query_camera(self.h, C.byref(q)))
+        return {k: v[:h * w].reshape((h, w) + tuple(v.shape[1:])) for k, v in out.items()}
+
     def synchronize(self):
         abi.check(self.lib, self.lib.rt_synchronize(self.h))
 

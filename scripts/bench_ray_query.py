@@ -8,7 +8,8 @@ records, closest hit with t only and any-hit, on
 
 as the median of --launches launches after --warmup warm-ups, timed with torch CUDA events on the query's stream.
 The closest-t run on (b) is repeated three times: the spread is what "any-hit is not slower than closest-t" is held
-to.  Next to them: the wall time of rt_trace_rays (host rays, the one-thread-per-ray kernel) on the same rays.
+to.  Next to them: the wall time of rt_trace_rays (host rays, the one-thread-per-ray kernel) on the same rays, and
+set (a) made by the library itself (a_camera_query: rt_query_camera, centre rays, t only, three runs).
 The refill threshold is a compile-time constant (RT_QUERY_THRESHOLD, csrc/ray_query.hpp): for a sweep, build variants
 with scripts/build_variant.sh and run this script per library through RTAMD_LIB.
 
@@ -16,6 +17,9 @@ with scripts/build_variant.sh and run this script per library through RTAMD_LIB.
                    range and one with tmax = 2.0, for a kernel trace that lists trace_rays_kernel's device time next
                    to ray_query_kernel's (rocprofv3 --kernel-trace --stats -- python scripts/bench_ray_query.py
                    --trace-once; the first ray_query_kernel dispatch is set (a), which makes set (b))
+  --camera         instead: rt_query_camera (centre rays; t only, records + albedo, rays only) against rt_query_rays on
+                   set (a) in a buffer, in row order and in 8x8-tile order, and against the torch expression that
+                   produces that buffer on the device; the variants alternated --repeats times in one process
   --out FILE       write the JSON there as well as to stdout
 """
 import argparse
@@ -33,7 +37,8 @@ for p in (REPO, os.path.join(REPO, "real-time-gpu-ray-tracer_amd")):
         sys.path.insert(0, p)
 
 
-def primary_rays(ci, w, h):
+def camera_frame(ci, w, h):
+    """(centre, pixel origin, dx, dy) of the camera's pixel grid (RenderPin.cu:73-95), float64."""
     v = lambda a: np.asarray([a.x, a.y, a.z], np.float64)
     center, target, up = v(ci.center), v(ci.target), v(ci.up)
     unit = lambda a: a / np.linalg.norm(a)
@@ -45,6 +50,11 @@ def primary_rays(ci, w, h):
     V = unit(np.cross(U, W))
     dx, dy = U * vw / w, V * vh / h
     po = center + W * fd - U * vw * 0.5 - V * vh * 0.5 + dx * 0.5 + dy * 0.5
+    return center, po, dx, dy
+
+
+def primary_rays(ci, w, h):
+    center, po, dx, dy = camera_frame(ci, w, h)
     px, py = np.meshgrid(np.arange(w), np.arange(h))
     d = po[None, None, :] + px[..., None] * dx + py[..., None] * dy - center
     d /= np.linalg.norm(d, axis=-1, keepdims=True)
@@ -76,7 +86,8 @@ def setup(config):
     return r, a, b, float(hit.mean())
 
 
-def timed(r, rays, tmax, launches, warmup, **kw):
+def timed_call(enqueue, n, launches, warmup):
+    """enqueue(): one launch (or torch expression) on torch's current stream, without a host wait."""
     import torch
     st = torch.cuda.Stream()
     # every launch is enqueued before the first wait: the host runs ahead of the device, so an interval holds the
@@ -86,13 +97,73 @@ def timed(r, rays, tmax, launches, warmup, **kw):
         for i in range(warmup + launches):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(st)
-            r.query_rays(rays, tmax, sync=False, **kw)
+            enqueue()
             e1.record(st)
             ev.append((e0, e1))
     st.synchronize()
     ms = [e0.elapsed_time(e1) for e0, e1 in ev[warmup:]]
     med = statistics.median(ms)
-    return {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "Mrays_s": round(len(rays) / med / 1e3, 1)}
+    return {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "Mrays_s": round(n / med / 1e3, 1)}
+
+
+def timed(r, rays, tmax, launches, warmup, **kw):
+    return timed_call(lambda: r.query_rays(rays, tmax, sync=False, **kw), len(rays), launches, warmup)
+
+
+def primary_rays_device(ci, w, h):
+    """primary_rays as a torch expression on the device (float32): the producer of the buffer a caller without
+    rt_query_camera has to run before rt_query_rays.  The camera frame's nine vectors are host values."""
+    import torch
+    center, po, dx, dy = camera_frame(ci, w, h)
+    dev = lambda a: torch.tensor(a, dtype=torch.float32, device="cuda")
+    t_po, t_dx, t_dy, t_c = dev(po - center), dev(dx), dev(dy), dev(center)
+    xs = torch.arange(w, dtype=torch.float32, device="cuda")
+    ys = torch.arange(h, dtype=torch.float32, device="cuda")
+
+    def produce():
+        d = t_po + xs[None, :, None] * t_dx + ys[:, None, None] * t_dy
+        d = d * torch.rsqrt((d * d).sum(-1, keepdim=True))
+        return torch.cat([t_c.expand(h, w, 3), d], -1).reshape(-1, 6)
+    return produce
+
+
+def measure_camera(args):
+    """rt_query_camera (centre rays) against rt_query_rays on the same rays held in a buffer, in one process, the
+    variants alternated --repeats times after one pass that warms every shape (profiles/camera_query/README.md)."""
+    import torch
+    r, a, _, hit_frac = setup(args.config)
+    w, h = r.width, r.height
+    n = w * h
+    tiles = np.arange(n).reshape(h // 8, 8, w // 8, 8).transpose(0, 2, 1, 3).reshape(-1)
+    d_rows = torch.from_numpy(a).cuda()
+    d_tiles = torch.from_numpy(a[tiles]).cuda()
+    produce = primary_rays_device(r.camera, w, h)
+    variants = {
+        "camera_t": lambda: r.query_camera(sync=False),
+        "camera_hits_albedo": lambda: r.query_camera(want_t=False, want_hits=True, want_albedo=True, sync=False),
+        "camera_rays_only": lambda: r.query_camera(want_t=False, want_rays=True, sync=False),
+        "a_primary": lambda: r.query_rays(d_rows, None, want_hits=False, sync=False),
+        "a_primary_8x8_tiles": lambda: r.query_rays(d_tiles, None, want_hits=False, sync=False),
+        "a_primary_records": lambda: r.query_rays(d_rows, None, sync=False),
+        "producer_torch": produce,
+    }
+    # the camera query's t against the buffer query's on the script's own rays (float64-built, so not bit-equal rays)
+    t_cam = r.query_camera()["t"].reshape(-1)
+    t_buf, _ = r.query_rays(d_rows, None, want_hits=False)
+    same = float(((t_cam == t_buf) | ((t_cam - t_buf).abs() <= 1e-4 * t_buf.abs())).float().mean())
+    out = {"config": args.config, "build": "sah", "width": w, "height": h, "launches": args.launches,
+           "warmup": args.warmup, "repeats": args.repeats, "primary_hit_fraction": round(hit_frac, 4),
+           "t_agree_fraction": round(same, 6), "lib": os.path.basename(os.environ.get("RTAMD_LIB", "librtamd.so"))}
+    for fn in variants.values():                          # warm every shape first
+        timed_call(fn, n, 3, 2)
+    res = {k: [] for k in variants}
+    for _ in range(args.repeats):
+        for k, fn in variants.items():
+            res[k].append(timed_call(fn, n, args.launches, args.warmup)["ms_median"])
+    for k, v in res.items():
+        out[k] = {"ms_medians": v, "ms_median": round(statistics.median(v), 4), "spread": round(max(v) - min(v), 4)}
+    r.cleanup()
+    return out
 
 
 def measure(args):
@@ -120,6 +191,10 @@ def measure(args):
             w.append((time.perf_counter() - t0) * 1e3)
         res["rt_trace_rays_wall_ms"] = round(min(w), 3)
         out[name] = res
+    # set (a) made by the library itself: rt_query_camera, centre rays, t only (--camera has the full comparison)
+    n = cfg_w * cfg_h
+    out["a_camera_query"] = {"rays": n, "closest_t": [timed_call(lambda: r.query_camera(sync=False), n, args.launches,
+                                                                 args.warmup) for _ in range(3)]}
     r.cleanup()
     return out
 
@@ -130,6 +205,8 @@ def main():
     p.add_argument("--launches", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--trace-once", action="store_true")
+    p.add_argument("--camera", action="store_true")
+    p.add_argument("--repeats", type=int, default=5)
     p.add_argument("--out")
     args = p.parse_args()
     if args.trace_once:
@@ -142,7 +219,7 @@ def main():
         print(json.dumps({"rays": len(b), "hit_fraction": round(float((h["instance"] != 0xFFFFFFFF).mean()), 4)}))
         r.cleanup()
         return
-    out = measure(args)
+    out = measure_camera(args) if args.camera else measure(args)
     line = json.dumps(out)
     print(line, flush=True)
     if args.out:

@@ -6,7 +6,10 @@ GPU-built scenes without cold records).  usage: scripts/kernel_resources.py real
 --hash: instead, for every object given (any object that holds kernels), the sha256 (first 16 hex digits) of its gfx950
 code object's .text bytes, .rodata bytes and `llvm-readelf --notes` output (kernel descriptors: registers, LDS, scratch,
 arguments).  A refactor that must not change the device code compares these between a build of the parent commit and
-one of the branch (profiles/refactor_*/README.md).  usage: scripts/kernel_resources.py --hash build/*.o"""
+one of the branch (profiles/refactor_*/README.md).  usage: scripts/kernel_resources.py --hash build/*.o
+
+--all: registers, spills, private segment and LDS of every kernel in the objects, by demangled name (the query kernels
+next to the render kernels: profiles/camera_query/kernel_resources.txt)."""
 import hashlib
 import re
 import subprocess
@@ -54,8 +57,24 @@ def print_resources(obj):
               f"sgpr {g('sgpr_count'):>3} sspill {g('sgpr_spill_count'):>3} scratch {g('private_segment_fixed_size')}")
 
 
+def print_all(obj):
+    """Every kernel of the object, by demangled name: registers, spills, private segment, LDS."""
+    with tempfile.TemporaryDirectory() as d:
+        notes = notes_of(code_object(obj, d))
+    rows = []
+    for e in notes.split("- .agpr_count")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", e).group(1)
+        dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+        dem = re.sub(r"\(.*", "", re.sub(r"rtamd::dev_\w+::", "", dem)).replace("void ", "")
+        g = lambda k: re.search(rf"\.{k}:\s+(\d+)", e).group(1)
+        rows.append(f"{obj.split('/')[-1]:18s} {dem:46s} vgpr {g('vgpr_count'):>3} vspill {g('vgpr_spill_count'):>3} "
+                    f"sgpr {g('sgpr_count'):>3} sspill {g('sgpr_spill_count'):>3} scratch {g('private_segment_fixed_size'):>4} "
+                    f"lds {g('group_segment_fixed_size'):>6}")
+    print("\n".join(sorted(rows)))
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
-    hashes = "--hash" in args
-    for obj in (a for a in args if a != "--hash"):
-        (print_hashes if hashes else print_resources)(obj)
+    mode = print_hashes if "--hash" in args else (print_all if "--all" in args else print_resources)
+    for obj in (a for a in args if a not in ("--hash", "--all")):
+        mode(obj)
