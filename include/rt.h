@@ -34,7 +34,8 @@ extern "C" {
  * 4: rt_query_rays
  * 5: rt_scene_update_triangles_device
  *    (RT_TRI_UPDATE_BOUNDS arrived within 5: a flag value that was rejected before is accepted now;
- *     rt_query_camera / rt_camera_query arrived within 5: a new entry point, no existing struct changed) */
+ *     rt_query_camera / rt_camera_query arrived within 5: a new entry point, no existing struct changed;
+ *     rt_denoise / rt_denoise_scratch_bytes / rt_denoise_desc arrived within 5 the same way) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -443,6 +444,67 @@ typedef struct rt_camera_query {
 } rt_camera_query;                  /* 72 bytes on LP64 */
 
 rt_status rt_query_camera(rt_scene *scene, const rt_camera_query *query);
+
+/* Denoising: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a frame in device memory, guided by
+ * the rt_hit records and, optionally, the albedo that rt_query_camera writes for the same pixels (csrc/denoise.hip).
+ * The call takes a device, like rt_box_test, and no scene: it reads nothing of one, and its only ordering is the
+ * stream's.  It allocates nothing.
+ *
+ * Inputs   : contiguous row-major width x height buffers.  color_device: 3 floats per pixel, what rt_render writes to
+ *            rgb32_device.  hits_device: what rt_query_camera writes to hits_device for the same rectangle; only
+ *            instance (0xFFFFFFFF = miss), point and normal are read.  albedo_device (optional): 3 floats per pixel.
+ * Filter   : per pixel p, miss(p) = (hits[p].instance == 0xFFFFFFFF); n(p), x(p) = the record's normal and point as
+ *            stored (0 in a miss record); a(p) = max(albedo(p), 1e-3) per channel, 1 without albedo; c_0 = color / a.
+ *            Pass i = 0 .. iterations - 1 has step s = 2^i and sigma_c,i = sigma_color * 2^-i:
+ *              c_{i+1}(p) = sum_q h(q) w(p, q) c_i(q) / sum_q h(q) w(p, q),  q = p + s * (dx, dy), dx, dy in -2 .. 2,
+ *              taps outside the image left out; h = k[dx] * k[dy], k = (1/16, 1/4, 3/8, 1/4, 1/16) (B3 spline);
+ *              w(p, q) = 0 when miss(p) != miss(q), else
+ *              exp(-(|c_i(p) - c_i(q)|^2 / sigma_c,i^2 + |n(p) - n(q)|^2 / sigma_normal^2
+ *                    + (n(p) . (x(q) - x(p)))^2 / sigma_plane^2)).
+ *            A sigma of +inf contributes 0 (its term is switched off).  The centre tap has w = 1, so the denominator
+ *            is at least 9/64.  Hits blend only with hits, sky only with sky.  The result is c_iterations * a.
+ *            In float32, without FMA contraction, taps summed row by row (dy, then dx, ascending); each term is
+ *            multiplied by 1 / sigma^2, computed once per pass and capped at FLT_MAX.
+ * Outputs  : at least one.  rgb32_device: 3 floats per pixel, the result; it may be color_device itself (the first
+ *            pass copies what it needs into the scratch, so the call works in place at any iteration count).
+ *            rgba8_device: uchar4 per pixel, Color3::castToUchar4 of the result as rt_render's rgba8 has it
+ *            (correctly rounded sqrt, clamp to [0, 0.999], x 256; alpha 255).  No other buffers may overlap.
+ * Scratch  : scratch_device holds at least rt_denoise_scratch_bytes(width, height) bytes (64 per pixel), 16-byte
+ *            aligned, and is the call's only working memory; its contents afterwards are unspecified.  Calls that
+ *            may run concurrently need a scratch each.
+ * Ordering : everything is enqueued on `stream` (NULL: the device's null stream).  With RT_DENOISE_NO_SYNC the call
+ *            returns after the enqueue, else once the outputs are complete.  Render, camera query and denoiser on one
+ *            stream with their NO_SYNC flags need no host synchronisation between them.
+ * Errors   : all before anything is enqueued, the argument checks first (they answer without a GPU):
+ *            RT_ERR_INVALID_ARGUMENT for a NULL desc, reserved != 0, unknown flags, iterations outside 1..5, a sigma
+ *            that is not > 0 (NaN included), width or height above 16384, no output buffer, a NULL color_device,
+ *            hits_device or scratch_device, scratch_bytes too small, a scratch not 16-byte aligned or another buffer
+ *            not 4-byte aligned; then for no such device, or a buffer that hipPointerGetAttributes does not report as
+ *            accessible from it.  width * height == 0 with otherwise valid arguments returns RT_OK and touches no
+ *            device.  The caller's current device is preserved.  Non-finite input colours are not detected: a NaN or
+ *            infinity spreads to the pixels whose taps reach it. */
+typedef enum rt_denoise_flags { RT_DENOISE_NO_SYNC = 1u << 2 } rt_denoise_flags;   /* the queries' NO_SYNC bit */
+
+typedef struct rt_denoise_desc {
+    uint32_t width, height;        /* each <= 16384; buffers are contiguous row-major W x H */
+    uint32_t iterations;           /* 1..5: steps 1, 2, 4, 8, 16 */
+    uint32_t flags;
+    float sigma_color;             /* > 0; +inf switches the term off; halved every pass */
+    float sigma_normal;            /* > 0; +inf off */
+    float sigma_plane;             /* > 0, world units; +inf off */
+    uint32_t reserved;             /* 0 */
+    const float  *color_device;    /* 3 floats per pixel: what rt_render writes to rgb32_device */
+    const rt_hit *hits_device;     /* what rt_query_camera writes to hits_device for the same rectangle */
+    const float  *albedo_device;   /* optional, 3 floats per pixel: demodulate before, remodulate after */
+    float  *rgb32_device;          /* optional output, 3 floats per pixel; may be color_device itself */
+    void   *rgba8_device;          /* optional output, uchar4 per pixel: Color3::castToUchar4 of the result */
+    void   *scratch_device;        /* >= rt_denoise_scratch_bytes(width, height) bytes, 16-byte aligned */
+    uint64_t scratch_bytes;
+    void   *stream;                /* hipStream_t; NULL = the device's null stream */
+} rt_denoise_desc;                 /* 96 bytes on LP64 */
+
+uint64_t  rt_denoise_scratch_bytes(uint32_t width, uint32_t height);
+rt_status rt_denoise(int device, const rt_denoise_desc *desc);
 
 /* The box decisions of the trace kernels on caller data, for parity tests (no scene needed): box i =
  * {xmin, xmax, ymin, ymax, zmin, zmax} (6 floats), ray i = origin xyz, direction xyz, range [0.001, tmax[i]].

@@ -1,5 +1,5 @@
 // launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
-// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip) and the host files that call them
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, denoise.hip) and the host files that call them
 // include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
 #pragma once
 
@@ -60,6 +60,21 @@ struct InstBoundsGPU {
     float4 *cent;                      // one per record: instances, then groups
 };
 hipError_t launch_inst_bounds(const InstBoundsGPU &b, const float *raw_verts, uint64_t first, uint64_t count, hipStream_t stream);
+// denoise.hip (rt_denoise): the caller's buffers and the four planes of its scratch, w * h float4 each
+struct DenoiseGPU {
+    const float *color;                // 3 floats per pixel
+    const rt_hit *hits;
+    const float *albedo;               // optional
+    float *rgb;                        // optional output, may be `color`
+    uint32_t *rgba;                    // optional output
+    float4 *plane[2];                  // the passes' colour planes: pass i reads plane[i & 1]
+    float4 *g0, *g1;                   // guides: {normal, flag}, {point, 0}
+    uint32_t w, h;
+};
+constexpr uint64_t DENOISE_SCRATCH_PER_PIXEL = 4 * sizeof(float4);
+// the pack pass and `iterations` (1..5) filter passes, the last one writing the outputs
+hipError_t launch_denoise(const DenoiseGPU &g, uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane,
+                          hipStream_t stream);
 
 // One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
 struct TraceFlavour {

@@ -1,4 +1,5 @@
-// render.cpp — the launches: a frame (rt_render and its steps), the tile assembly, the ray queries, the box test.
+// render.cpp — the launches: a frame (rt_render and its steps), the tile assembly, the ray queries, the box test,
+// the denoiser.
 // A frame issues its HIP calls in one fixed order on the frame's stream; the comments say what each wait and each
 // event record costs, so a step moves as a whole or not at all.
 #include "launch.hpp"
@@ -652,6 +653,52 @@ rt_status rt_box_test(int device, const float *boxes, const float *rays, const f
     if (e == hipSuccess) e = hipMemcpy(te, de, n * sizeof(float), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, std::string("rt_box_test: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+uint64_t rt_denoise_scratch_bytes(uint32_t width, uint32_t height) {
+    return (uint64_t)width * height * DENOISE_SCRATCH_PER_PIXEL;
+}
+
+rt_status rt_denoise(int device, const rt_denoise_desc *d) {
+    // the argument checks need no device
+    if (!d) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (d->reserved != 0 || (d->flags & ~(uint32_t)RT_DENOISE_NO_SYNC))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: reserved bits set");
+    if (d->iterations < 1 || d->iterations > 5) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: iterations must be in 1..5");
+    if (!(d->sigma_color > 0.0f) || !(d->sigma_normal > 0.0f) || !(d->sigma_plane > 0.0f))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: every sigma must be > 0 (+inf switches its term off)");
+    if (d->width > 16384 || d->height > 16384) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: width and height are at most 16384");
+    if (!d->rgb32_device && !d->rgba8_device) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: no output buffer");
+    if (!d->color_device || !d->hits_device || !d->scratch_device) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (d->scratch_bytes < rt_denoise_scratch_bytes(d->width, d->height))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: scratch_bytes is less than rt_denoise_scratch_bytes(width, height)");
+    if ((uintptr_t)d->scratch_device & 15u) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: the scratch must be 16-byte aligned");
+    if (((uintptr_t)d->color_device | (uintptr_t)d->hits_device | (uintptr_t)d->albedo_device | (uintptr_t)d->rgb32_device |
+         (uintptr_t)d->rgba8_device) & 3u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: the buffers must be 4-byte aligned");
+    if (d->width == 0 || d->height == 0) return RT_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
+        return fail(RT_ERR_INVALID_ARGUMENT, "no such device");
+    DeviceRestore restore;
+    HIP_TRY(hipSetDevice(device));
+    const void *bufs[] = {d->color_device, d->hits_device, d->albedo_device, d->rgb32_device, d->rgba8_device, d->scratch_device};
+    for (const void *p : bufs)
+        if (p && !device_accessible(p, device))
+            return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise: a buffer is not accessible from the device");
+
+    DenoiseGPU g{};
+    g.color = d->color_device; g.hits = d->hits_device; g.albedo = d->albedo_device;
+    g.rgb = d->rgb32_device; g.rgba = static_cast<uint32_t *>(d->rgba8_device);
+    const size_t n = (size_t)d->width * d->height;
+    float4 *scratch = static_cast<float4 *>(d->scratch_device);            // colour plane 0 | colour plane 1 | guides
+    g.plane[0] = scratch; g.plane[1] = scratch + n; g.g0 = scratch + 2 * n; g.g1 = scratch + 3 * n;
+    g.w = d->width; g.h = d->height;
+    hipStream_t st = static_cast<hipStream_t>(d->stream);
+    HIP_TRY(launch_denoise(g, d->iterations, d->sigma_color, d->sigma_normal, d->sigma_plane, st));
+    if (d->flags & RT_DENOISE_NO_SYNC) return RT_OK;
+    HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
 }
 

@@ -38,6 +38,8 @@ RT_CAMERA_QUERY_EXACT = 1 << 0
 RT_CAMERA_QUERY_NO_SYNC = 1 << 2
 RT_CAMERA_QUERY_FIRST_SAMPLE = 1 << 3
 
+RT_DENOISE_NO_SYNC = 1 << 2
+
 RT_TRI_UPDATE_NO_SYNC = 1 << 0
 RT_TRI_UPDATE_BOUNDS = 1 << 1
 
@@ -145,6 +147,15 @@ class CameraQuery(C.Structure):
                 ("albedo_device", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class DenoiseDesc(C.Structure):
+    """rt_denoise_desc: image size, passes, sigmas, device buffers, scratch and stream of one rt_denoise call."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("reserved", C.c_uint32), ("color_device", C.c_void_p), ("hits_device", C.c_void_p),
+                ("albedo_device", C.c_void_p), ("rgb32_device", C.c_void_p), ("rgba8_device", C.c_void_p),
+                ("scratch_device", C.c_void_p), ("scratch_bytes", C.c_uint64), ("stream", C.c_void_p)]
+
+
 class TriangleUpdate(C.Structure):
     """rt_triangle_update: triangle range, device vertex / normal streams and stream of one
     rt_scene_update_triangles_device call."""
@@ -204,6 +215,7 @@ EXPORTED_SYMBOLS = (
     "rt_comm_unique_id", "rt_scene_attach_comm", "rt_scene_detach_comm", "rt_slab_tiles", "rt_tile_pixels",
     "rt_comm_set_timeout", "rt_camera_control_init", "rt_camera_move", "rt_clock_ns", "rt_frame_pace",
     "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device", "rt_query_camera",
+    "rt_denoise", "rt_denoise_scratch_bytes",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -235,6 +247,10 @@ def _declare(lib):
     lib.rt_query_rays.restype = C.c_int
     lib.rt_query_camera.argtypes = [C.c_void_p, P(CameraQuery)]
     lib.rt_query_camera.restype = C.c_int
+    lib.rt_denoise.argtypes = [C.c_int, P(DenoiseDesc)]
+    lib.rt_denoise.restype = C.c_int
+    lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    lib.rt_denoise_scratch_bytes.restype = C.c_uint64
     lib.rt_synchronize.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.restype = None

@@ -24,6 +24,11 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("instance", np.uint32), ("ptype", np.u
                       ("mtype", np.uint32), ("midx", np.uint32)])     # rt_hit, as Renderer.trace_rays returns it
 
 
+# Renderer.denoise's default (sigma_color, sigma_normal, sigma_plane): the best point of the grid in
+# profiles/denoise/README.md (the C2 scene at 1080p, 1 sample per pixel, against 1 024 samples)
+DENOISE_SIGMAS = (3.0, 0.1, 0.1)
+
+
 def hits_to_numpy(hits) -> np.ndarray:
     """The rt_hit records of Renderer.query_rays (torch uint8 [N, 48], any device) as the structured array
     Renderer.trace_rays returns."""
@@ -371,6 +376,70 @@ class Renderer:
                     out[key] = buf
         abi.check(self.lib, self.lib.rt_query_camera(self.h, C.byref(q)))
         return {k: v[:h * w].reshape((h, w) + tuple(v.shape[1:])) for k, v in out.items()}
+
+    def denoise(self, rgb, hits, albedo=None, *, iterations: int = 5, sigma_color: float = DENOISE_SIGMAS[0],
+                sigma_normal: float = DENOISE_SIGMAS[1], sigma_plane: float = DENOISE_SIGMAS[2],
+                want_rgba: bool = False, out=None, stream=None, sync: bool = True):
+        """rt_denoise: the edge-avoiding a-trous filter (include/rt.h, "Denoising") on torch CUDA tensors of the
+        shapes render and query_camera produce: rgb float32 [h, w, 3] (a frame rendered into rgb32_device), hits uint8
+        [h, w, 48] (query_camera(want_hits=True)) and optionally albedo float32 [h, w, 3] (want_albedo=True), all
+        contiguous and on the scene's device.  The sigma defaults are the best point of the grid in
+        profiles/denoise/README.md; float("inf") switches a term off.  out: the float32 [h, w, 3] tensor to write,
+        which may be rgb itself (None: a new one).  Returns {"rgb": out} and, with want_rgba, "rgba" uint8 [h, w, 4].
+        stream: a torch.cuda.Stream or a raw hipStream_t (None = torch's current stream); the scratch and the outputs
+        are allocated on it, and with sync=False the call returns after the enqueue."""
+        import torch                              # here: `import rtamd` needs no torch
+
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+
+        def checked(x, tail, dtype, name):
+            if not isinstance(x, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor")
+            if x.dtype != dtype:
+                raise ValueError(f"{name}: {dtype}, not {x.dtype}")
+            if x.device != dev:
+                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+            if x.dim() != 3 or x.shape[2] != tail:
+                raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+            return x
+
+        rgb = checked(rgb, 3, torch.float32, "rgb")
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        for x, tail, dtype, name in ((hits, C.sizeof(abi.Hit), torch.uint8, "hits"), (albedo, 3, torch.float32, "albedo"),
+                                     (out, 3, torch.float32, "out")):
+            if x is not None or name == "hits":
+                if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
+                    raise ValueError(f"{name}: {tuple(x.shape[:2])}, rgb is {(h, w)}")
+        if not isinstance(stream, torch.cuda.Stream):
+            sync = True      # a raw hipStream_t gives torch nothing to order the scratch's release with (as query_rays)
+        d = abi.DenoiseDesc()
+        d.width, d.height, d.iterations = w, h, int(iterations)
+        d.flags = 0 if sync else abi.RT_DENOISE_NO_SYNC
+        d.sigma_color, d.sigma_normal, d.sigma_plane = float(sigma_color), float(sigma_normal), float(sigma_plane)
+        d.scratch_bytes = self.lib.rt_denoise_scratch_bytes(w, h)
+        d.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        with ctx:                                 # made on the call's stream, as query_camera's outputs
+            if out is None:
+                out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+            rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if want_rgba else None
+            scratch = torch.empty(max(int(d.scratch_bytes), 16), dtype=torch.uint8, device=dev)
+        res = {"rgb": out}
+        if want_rgba:
+            res["rgba"] = rgba
+        if h * w == 0:
+            return res
+        d.color_device, d.hits_device = rgb.data_ptr(), hits.data_ptr()
+        d.albedo_device = albedo.data_ptr() if albedo is not None else None
+        d.rgb32_device = out.data_ptr()
+        d.rgba8_device = rgba.data_ptr() if want_rgba else None
+        d.scratch_device = scratch.data_ptr()
+        abi.check(self.lib, self.lib.rt_denoise(self.device, C.byref(d)))
+        return res
 
     def synchronize(self):
         abi.check(self.lib, self.lib.rt_synchronize(self.h))
