@@ -35,7 +35,8 @@ extern "C" {
  * 5: rt_scene_update_triangles_device
  *    (RT_TRI_UPDATE_BOUNDS arrived within 5: a flag value that was rejected before is accepted now;
  *     rt_query_camera / rt_camera_query arrived within 5: a new entry point, no existing struct changed;
- *     rt_denoise / rt_denoise_scratch_bytes / rt_denoise_desc arrived within 5 the same way) */
+ *     rt_denoise / rt_denoise_scratch_bytes / rt_denoise_desc arrived within 5 the same way;
+ *     rt_accumulate / rt_accumulate_desc / rt_camera_reprojection / rt_reprojection arrived within 5 the same way) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -505,6 +506,83 @@ typedef struct rt_denoise_desc {
 
 uint64_t  rt_denoise_scratch_bytes(uint32_t width, uint32_t height);
 rt_status rt_denoise(int device, const rt_denoise_desc *desc);
+
+/* Temporal accumulation: last frame's accumulated colour carried to this frame's pixels by reprojecting each pixel's
+ * hit point into the previous camera, and blended with this frame's colour (csrc/accumulate.hip).  Like rt_denoise the
+ * call takes a device and buffers, no scene; its only ordering is the stream's, and it allocates nothing.
+ *
+ * Reprojection: rt_camera_reprojection derives, on the host and without a scene or a GPU, the rows that map a world
+ *            point x to a camera's frame: v = x - centre, fx = (rx . v) / (rw . v), fy = (ry . v) / (rw . v); pixel
+ *            (i, j)'s centre lands on (fx, fy) = (i, j), and rw . v > 0 in front of the camera.  The camera is derived
+ *            as rt_camera_set derives it (one shared function); from its float pixel_origin, dx, dy and center, in
+ *            double: p0 = pixel_origin - center, det = dx . (dy x p0), rx = (dy x p0) / det, ry = (p0 x dx) / det,
+ *            rw = (dx x dy) / det, each rounded to float.  RT_ERR_INVALID_ARGUMENT for a NULL argument, a width or
+ *            height of 0 or above 32768, or a non-finite result (center == target is one such camera).  The focus
+ *            disk is ignored: the rows describe the pinhole through `center`.
+ * Inputs   : contiguous row-major width x height buffers.  color_device: this frame, 3 floats per pixel (rt_render's
+ *            rgb32_device).  hits_device: this frame's rt_query_camera records; prev_hits_device: last frame's.
+ *            prev_history_device: the history_device of the last call, float4 {r, g, b, length} per pixel.
+ *            prev_view: a HOST pointer to the previous frame's rows, read during the call; NULL = the camera has not
+ *            moved, every pixel looks at itself.
+ * Filter   : for pixel p = (i, j), k = j W + i, c = color[k], rec = hits[k], n and x its normal and point as stored,
+ *            H(q) = prev_history[q].
+ *              reset(p): history[k] = (c, 1), rgb32[k] = c.  It applies when prev_history_device is NULL (the first
+ *              frame), when rec.instance == 0xFFFFFFFF (sky is the noise-free part of a frame and is not reused), and
+ *              whenever a test below fails.
+ *              Position: with prev_view NULL a single tap q = p with weight b = 1.  Otherwise v = x - centre per
+ *              component, r0 = (rx.x v.x + rx.y v.y) + rx.z v.z, r1 and r2 the same from ry and rw; reset unless
+ *              r2 > 0; fx = r0 / r2, fy = r1 / r2; reset unless fx >= -1 && fx < (float)W && fy >= -1 &&
+ *              fy < (float)H (a NaN fails every comparison); ix = floorf(fx), wx = fx - ix, likewise iy, wy; the taps
+ *              are (ix + tx, iy + ty) for (tx, ty) = (0,0), (1,0), (0,1), (1,1) in that order, with
+ *              b = (tx ? wx : 1 - wx) * (ty ? wy : 1 - wy).
+ *              A tap q is valid when it lies inside the image and, with m = prev_hits[q] and e = m.point - x:
+ *              m.instance == rec.instance; (n.x m.n.x + n.y m.n.y) + n.z m.n.z >= normal_cos;
+ *              fabsf((n.x e.x + n.y e.y) + n.z e.z) <= plane_tolerance * rec.t.
+ *              Blend: S = sum b H(q) over the four channels and D = sum b over the valid taps, both from 0 in tap
+ *              order, each product rounded before it is added; reset unless D > 0; Hm = S / D per channel;
+ *              N = fminf(Hm.w + 1, max_history), a = 1 / N; out.rgb = Hm.rgb + a (c - Hm.rgb), out.w = N;
+ *              history[k] = out, rgb32[k] = out.rgb.
+ *            In float32 without FMA contraction, IEEE division, no transcendental function: the float32 restatement
+ *            in tests/accumulate_ref.py gives the kernel's bits.
+ * Not done : instance motion is not compensated (a moved instance is caught only by the plane test, so its pixels
+ *            restart); no 3 x 3 fallback search around a failed reprojection; no luminance moments and no variance
+ *            guidance for rt_denoise; sky is not reused.
+ * Outputs  : history_device (required): float4 per pixel, next frame's prev_history_device.  rgb32_device (optional):
+ *            3 floats per pixel, out.rgb; it may be color_device itself (a thread reads only its own pixel's colour).
+ *            Otherwise no output may overlap an input or the other output: the byte ranges are compared on the host.
+ *            So the caller ping-pongs two history buffers and two hits buffers.
+ * Ordering : as rt_denoise, with RT_ACCUMULATE_NO_SYNC for RT_DENOISE_NO_SYNC.
+ * Errors   : all before anything is enqueued, the argument checks first (they answer without a GPU):
+ *            RT_ERR_INVALID_ARGUMENT for a NULL desc, reserved or reserved1 != 0, unknown flags, width or height above
+ *            16384, max_history not >= 1, normal_cos not <= 1, plane_tolerance not > 0 (NaN fails each), a NULL
+ *            color_device, hits_device or history_device, only one of prev_hits_device and prev_history_device, a
+ *            history buffer not 16-byte aligned or another buffer not 4-byte aligned, overlapping buffers as above;
+ *            then for no such device, or a buffer that hipPointerGetAttributes does not report as accessible from
+ *            it.  width * height == 0 with otherwise valid arguments returns RT_OK and touches no device.  The
+ *            caller's current device is preserved. */
+typedef struct rt_reprojection { float centre[3], rx[3], ry[3], rw[3]; } rt_reprojection;   /* 48 bytes */
+
+rt_status rt_camera_reprojection(const rt_camera_input *camera, uint32_t width, uint32_t height, rt_reprojection *out);
+
+typedef enum rt_accumulate_flags { RT_ACCUMULATE_NO_SYNC = 1u << 2 } rt_accumulate_flags;  /* the queries' NO_SYNC bit */
+
+typedef struct rt_accumulate_desc {
+    uint32_t width, height, flags, reserved;          /* reserved 0; width, height <= 16384 */
+    float max_history;                                /* >= 1, +inf allowed: blend weight never below 1 / max_history */
+    float normal_cos;                                 /* <= 1, not NaN; -inf switches the test off */
+    float plane_tolerance;                            /* > 0, a fraction of the pixel's hit distance t; +inf off */
+    uint32_t reserved1;                               /* 0 */
+    const rt_reprojection *prev_view;                 /* HOST pointer, read during the call; NULL = same pixel (static camera) */
+    const float  *color_device;                       /* 3 floats per pixel: this frame (rt_render's rgb32_device) */
+    const rt_hit *hits_device;                        /* this frame's rt_query_camera records */
+    const rt_hit *prev_hits_device;                   /* last frame's records; NULL with prev_history_device NULL = first frame */
+    const float  *prev_history_device;                /* last call's history_device: float4 {r, g, b, length} per pixel, 16-byte aligned */
+    float  *history_device;                           /* required output, float4 per pixel, 16-byte aligned */
+    float  *rgb32_device;                             /* optional output, 3 floats per pixel; may be color_device itself */
+    void   *stream;                                   /* hipStream_t; NULL = the device's null stream */
+} rt_accumulate_desc;                                 /* 96 bytes on LP64 */
+
+rt_status rt_accumulate(int device, const rt_accumulate_desc *desc);
 
 /* The box decisions of the trace kernels on caller data, for parity tests (no scene needed): box i =
  * {xmin, xmax, ymin, ymax, zmin, zmax} (6 floats), ray i = origin xyz, direction xyz, range [0.001, tmax[i]].

@@ -1,0 +1,133 @@
+// accumulate.hip — rt_accumulate: temporal accumulation by reprojecting each pixel's hit point into the last frame.
+// include/rt.h ("Temporal accumulation") states the filter; tests/accumulate_ref.py restates it in numpy with this
+// file's operation order.  Built with -ffp-contract=off; the kernel uses +, -, *, IEEE division, floorf, fabsf and
+// fminf only, so the float32 restatement gives its bits.
+//   One launch, one thread per pixel, no LDS.  A thread reads its colour (12 B), its rt_hit record (48 B: t, instance,
+//   point, normal are used), up to four of last frame's records and history texels, and writes a history texel (16 B)
+//   and optionally the colour (12 B): 152 B of compulsory traffic per pixel when neighbouring lanes' taps share the
+//   previous records.  Records are 4-byte aligned by contract, so they are read with dword loads; the history planes
+//   are float4.
+//   Two pixel-to-lane mappings, same arithmetic and so the same bits (ACC_FORM):
+//     rows    blockDim (64, 4): a wave is 64 consecutive pixels of a row; its own records are one contiguous 3 KiB.
+//     blocks  a 16 x 16 tile per workgroup, a wave an 8 x 8 block of it: the four taps of neighbouring lanes share
+//             cache lines in both axes once the camera turns.
+//   Measured on C2's frames (profiles/accumulate/README.md): rows is 7 to 8 % faster with a still camera, and the two
+//   tie within 0.6 % when it moves, so rows is the default.
+// Every tap's coordinates are tested before its loads; pixel indices are size_t.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "launch.hpp"
+
+namespace rtamd {
+
+namespace {
+
+constexpr uint32_t ACC_MISS = 0xFFFFFFFFu;
+
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+    return (ax * bx + ay * by) + az * bz;
+}
+
+__device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, int j) {
+    const size_t k = (size_t)j * g.w + (size_t)i;
+    const float cr = g.color[3 * k + 0], cg = g.color[3 * k + 1], cb = g.color[3 * k + 2];
+    float4 out = make_float4(cr, cg, cb, 1.0f);                       // reset(p)
+    const rt_hit *rec = g.hits + k;
+    const uint32_t inst = rec->instance;
+    if (g.prev_history && inst != ACC_MISS) {
+        const float px = rec->point.x, py = rec->point.y, pz = rec->point.z;
+        const float nx = rec->normal.x, ny = rec->normal.y, nz = rec->normal.z;
+        const float tol = g.plane_tolerance * rec->t;
+        int ix = i, iy = j;
+        float wx = 0.0f, wy = 0.0f;
+        bool ok = true;
+        if (g.has_view) {
+            const rt_reprojection &m = g.view;
+            const float vx = px - m.centre[0], vy = py - m.centre[1], vz = pz - m.centre[2];
+            const float r0 = dot3(m.rx[0], m.rx[1], m.rx[2], vx, vy, vz);
+            const float r1 = dot3(m.ry[0], m.ry[1], m.ry[2], vx, vy, vz);
+            const float r2 = dot3(m.rw[0], m.rw[1], m.rw[2], vx, vy, vz);
+            const float fx = r0 / r2, fy = r1 / r2;
+            ok = r2 > 0.0f && fx >= -1.0f && fx < (float)g.w && fy >= -1.0f && fy < (float)g.h;
+            if (ok) {
+                const float flx = floorf(fx), fly = floorf(fy);
+                ix = (int)flx; iy = (int)fly;
+                wx = fx - flx; wy = fy - fly;
+            }
+        }
+        if (ok) {
+            float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, den = 0.0f;
+#pragma unroll
+            for (int tap = 0; tap < 4; tap++) {
+                const int tx = tap & 1, ty = tap >> 1;
+                if (!g.has_view && tap) break;
+                const int qx = ix + tx, qy = iy + ty;
+                if (qx < 0 || qy < 0 || qx >= (int)g.w || qy >= (int)g.h) continue;
+                const size_t q = (size_t)qy * g.w + (size_t)qx;
+                const rt_hit *m = g.prev_hits + q;
+                if (m->instance != inst) continue;
+                if (!(dot3(nx, ny, nz, m->normal.x, m->normal.y, m->normal.z) >= g.normal_cos)) continue;
+                const float ex = m->point.x - px, ey = m->point.y - py, ez = m->point.z - pz;
+                if (!(fabsf(dot3(nx, ny, nz, ex, ey, ez)) <= tol)) continue;
+                const float b = g.has_view ? (tx ? wx : 1.0f - wx) * (ty ? wy : 1.0f - wy) : 1.0f;
+                const float4 hq = g.prev_history[q];
+                sr = sr + b * hq.x;
+                sg = sg + b * hq.y;
+                sb = sb + b * hq.z;
+                sw = sw + b * hq.w;
+                den = den + b;
+            }
+            if (den > 0.0f) {
+                const float hr = sr / den, hg = sg / den, hb = sb / den, hw = sw / den;
+                const float n = fminf(hw + 1.0f, g.max_history);
+                const float a = 1.0f / n;
+                out = make_float4(hr + a * (cr - hr), hg + a * (cg - hg), hb + a * (cb - hb), n);
+            }
+        }
+    }
+    g.history[k] = out;
+    if (g.rgb) {
+        g.rgb[3 * k + 0] = out.x;
+        g.rgb[3 * k + 1] = out.y;
+        g.rgb[3 * k + 2] = out.z;
+    }
+}
+
+// blockDim (64, 4): a wave is 64 consecutive pixels of one row
+__global__ __launch_bounds__(256) void accumulate_rows_kernel(AccumulateGPU g) {
+    const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
+    if (x >= (int)g.w || y >= (int)g.h) return;
+    accumulate_pixel(g, x, y);
+}
+
+// blockDim 256, a 16 x 16 tile: wave w is the 8 x 8 block (w & 1, w >> 1) of it, lane l its pixel (l & 7, l >> 3)
+__global__ __launch_bounds__(256) void accumulate_blocks_kernel(AccumulateGPU g) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const int x = (int)(blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u));
+    const int y = (int)(blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3));
+    if (x >= (int)g.w || y >= (int)g.h) return;
+    accumulate_pixel(g, x, y);
+}
+
+// The mapping: 'r' rows, 'b' blocks.  scripts/accumulate_bench.py measures them side by side, alternating in one
+// process, through RTAMD_ACCUMULATE_FORM (read per call; anything but one valid letter is ignored); the default is
+// the faster of profiles/accumulate/README.md.
+constexpr char ACC_FORM = 'r';
+char pixel_mapping() {
+    const char *e = std::getenv("RTAMD_ACCUMULATE_FORM");
+    return e && (e[0] == 'r' || e[0] == 'b') && e[1] == 0 ? e[0] : ACC_FORM;
+}
+
+}  // namespace
+
+hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream) {
+    if (pixel_mapping() == 'r')
+        hipLaunchKernelGGL(accumulate_rows_kernel, dim3((g.w + 63u) / 64u, (g.h + 3u) / 4u), dim3(64, 4), 0, stream, g);
+    else
+        hipLaunchKernelGGL(accumulate_blocks_kernel, dim3((g.w + 15u) / 16u, (g.h + 15u) / 16u), dim3(256), 0, stream, g);
+    return hipGetLastError();
+}
+
+}  // namespace rtamd

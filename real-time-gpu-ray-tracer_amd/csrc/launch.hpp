@@ -1,5 +1,5 @@
 // launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
-// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, denoise.hip) and the host files that call them
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, denoise.hip, accumulate.hip) and the host files that call them
 // include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
 #pragma once
 
@@ -75,6 +75,20 @@ constexpr uint64_t DENOISE_SCRATCH_PER_PIXEL = 4 * sizeof(float4);
 // the pack pass and `iterations` (1..5) filter passes, the last one writing the outputs
 hipError_t launch_denoise(const DenoiseGPU &g, uint32_t iterations, float sigma_color, float sigma_normal, float sigma_plane,
                           hipStream_t stream);
+// accumulate.hip (rt_accumulate): the caller's buffers, the thresholds and the previous frame's rows
+struct AccumulateGPU {
+    const float *color;                // 3 floats per pixel
+    const rt_hit *hits, *prev_hits;    // prev_hits and prev_history: both or neither
+    const float4 *prev_history;
+    float4 *history;
+    float *rgb;                        // optional output, may be `color`
+    uint32_t w, h;
+    float max_history, normal_cos, plane_tolerance;
+    uint32_t has_view;                 // 0: every pixel looks at itself and `view` is not read
+    rt_reprojection view;
+};
+// one launch, one thread per pixel
+hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream);
 
 // One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
 struct TraceFlavour {

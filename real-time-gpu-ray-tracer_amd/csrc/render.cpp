@@ -1,5 +1,5 @@
 // render.cpp — the launches: a frame (rt_render and its steps), the tile assembly, the ray queries, the box test,
-// the denoiser.
+// the denoiser, the temporal accumulation.
 // A frame issues its HIP calls in one fixed order on the frame's stream; the comments say what each wait and each
 // event record costs, so a step moves as a whole or not at all.
 #include "launch.hpp"
@@ -698,6 +698,64 @@ rt_status rt_denoise(int device, const rt_denoise_desc *d) {
     hipStream_t st = static_cast<hipStream_t>(d->stream);
     HIP_TRY(launch_denoise(g, d->iterations, d->sigma_color, d->sigma_normal, d->sigma_plane, st));
     if (d->flags & RT_DENOISE_NO_SYNC) return RT_OK;
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+rt_status rt_accumulate(int device, const rt_accumulate_desc *d) {
+    // the argument checks need no device
+    if (!d) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (d->reserved != 0 || d->reserved1 != 0 || (d->flags & ~(uint32_t)RT_ACCUMULATE_NO_SYNC))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: reserved bits set");
+    if (d->width > 16384 || d->height > 16384) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: width and height are at most 16384");
+    if (!(d->max_history >= 1.0f)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: max_history must be >= 1");
+    if (!(d->normal_cos <= 1.0f)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: normal_cos must be <= 1 (-inf switches the test off)");
+    if (!(d->plane_tolerance > 0.0f))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: plane_tolerance must be > 0 (+inf switches the test off)");
+    if (!d->color_device || !d->hits_device || !d->history_device) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!d->prev_hits_device != !d->prev_history_device)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: prev_hits_device and prev_history_device go together");
+    if (((uintptr_t)d->history_device | (uintptr_t)d->prev_history_device) & 15u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: the history buffers must be 16-byte aligned");
+    if (((uintptr_t)d->color_device | (uintptr_t)d->hits_device | (uintptr_t)d->prev_hits_device | (uintptr_t)d->rgb32_device) & 3u)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: the buffers must be 4-byte aligned");
+    // no output may overlap an input or the other output; rgb32_device may be color_device itself
+    const uint64_t n = (uint64_t)d->width * d->height;
+    struct Range { const void *p; uint64_t bytes; };
+    const Range history{d->history_device, 16 * n}, rgb{d->rgb32_device, 12 * n};
+    const Range read[] = {{d->hits_device, sizeof(rt_hit) * n}, {d->prev_hits_device, sizeof(rt_hit) * n},
+                          {d->prev_history_device, 16 * n}};
+    const Range color{d->color_device, 12 * n};
+    auto overlap = [](const Range &x, const Range &y) {
+        const uintptr_t a = (uintptr_t)x.p, b = (uintptr_t)y.p;
+        return x.p && y.p && a < b + y.bytes && b < a + x.bytes;
+    };
+    bool clash = overlap(history, rgb) || overlap(history, color) || (rgb.p != color.p && overlap(rgb, color));
+    for (const Range &r : read) clash = clash || overlap(history, r) || overlap(rgb, r);
+    if (clash) return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: an output overlaps another buffer");
+    if (n == 0) return RT_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
+        return fail(RT_ERR_INVALID_ARGUMENT, "no such device");
+    DeviceRestore restore;
+    HIP_TRY(hipSetDevice(device));
+    const void *bufs[] = {d->color_device, d->hits_device, d->prev_hits_device, d->prev_history_device, d->history_device,
+                          d->rgb32_device};
+    for (const void *p : bufs)
+        if (p && !device_accessible(p, device))
+            return fail(RT_ERR_INVALID_ARGUMENT, "rt_accumulate: a buffer is not accessible from the device");
+
+    AccumulateGPU g{};
+    g.color = d->color_device; g.hits = d->hits_device; g.prev_hits = d->prev_hits_device;
+    g.prev_history = reinterpret_cast<const float4 *>(d->prev_history_device);
+    g.history = reinterpret_cast<float4 *>(d->history_device);
+    g.rgb = d->rgb32_device;
+    g.w = d->width; g.h = d->height;
+    g.max_history = d->max_history; g.normal_cos = d->normal_cos; g.plane_tolerance = d->plane_tolerance;
+    if (d->prev_view) { g.has_view = 1; g.view = *d->prev_view; }
+    hipStream_t st = static_cast<hipStream_t>(d->stream);
+    HIP_TRY(launch_accumulate(g, st));
+    if (d->flags & RT_ACCUMULATE_NO_SYNC) return RT_OK;
     HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
 }

@@ -16,7 +16,7 @@
 //   blas_gpu.cpp    the GPU BLAS builds of RT_BUILD_LBVH and their segments
 //   update.cpp      rt_scene_update_triangles / _triangles_device / _instances, the device-bounds state
 //   render.cpp      rt_render with auto_lanes and order_null, rt_assemble_tiles, rt_trace_rays, rt_query_rays, rt_query_camera,
-//                   rt_box_test, rt_denoise (its kernels: denoise.hip)
+//                   rt_box_test, rt_denoise (its kernels: denoise.hip), rt_accumulate (accumulate.hip)
 //   scene_comm.cpp  the RCCL attach / detach / abort path and a frame's gather
 //   debug.cpp       rt_scene_debug_read, rt_scene_export_blas / _tlas
 #include "scene.hpp"
@@ -45,6 +45,34 @@ void fill_stats(rt_stats *st, const unsigned long long *c) {
     st->quad_tests = c[CNT_QUAD];
     st->instance_visits = c[CNT_INST];
     st->hits = c[CNT_HITS];
+}
+
+// The camera rt_camera_set hands the kernels, from the caller's description: RendererImpl::calculateCameraProperties
+// (src/Global/RenderPin.cu:73-95).  rt_camera_reprojection derives its rows from the same floats.
+static void derive_camera(const rt_camera_input *c, uint32_t w, uint32_t h, CameraGPU &g) {
+    using namespace hm;
+    const V3 center = of(c->center), target = of(c->target), up = of(c->up);
+    const float fd = distance(center, target);
+    const float theta = c->fov * PI / 180.0f;
+    const float vw = 2.0f * std::tan(theta / 2.0f) * fd;
+    const float vh = vw / ((float)w * 1.0f / (float)h);
+    const V3 W = unit(target - center);
+    const V3 U = unit(cross(W, up));
+    const V3 V = unit(cross(U, W));
+    const V3 vx = U * vw, vy = V * vh;
+    const V3 dx = vx / (float)w, dy = vy / (float)h;
+    const V3 vorg = center + W * fd - vx * 0.5f - vy * 0.5f;
+    const V3 po = vorg + dx * 0.5f + dy * 0.5f;
+    for (int a = 0; a < 3; a++) {
+        g.pixel_origin[a] = po[a]; g.dx[a] = dx[a]; g.dy[a] = dy[a]; g.center[a] = center[a];
+        g.cu[a] = U[a]; g.cv[a] = V[a]; g.background[a] = of(c->background)[a];
+    }
+    g.focus_radius = c->focus_disk_radius;
+    g.sqrt_s = (uint32_t)std::sqrt((double)c->sample_count);            // RenderPin.cu:93
+    g.recip_sqrt = 1.0f / (float)g.sqrt_s;                              // RenderPin.cu:94
+    g.depth = c->ray_trace_depth;
+    g.width = w; g.height = h;
+    g.pitch = (w + 15u) / 16u * 16u;                                    // 16x16 blocks (SDL_OpenGLWindow.cu:119-122)
 }
 
 }  // namespace rtamd
@@ -98,33 +126,37 @@ rt_status rt_camera_set(rt_scene *s, const rt_camera_input *c, uint32_t w, uint3
     if (!s || !c) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
     if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(RT_ERR_INVALID_ARGUMENT, "bad framebuffer size");
     if (c->sample_count == 0) return fail(RT_ERR_INVALID_ARGUMENT, "sample_count must be >= 1");
-    // RendererImpl::calculateCameraProperties (src/Global/RenderPin.cu:73-95)
-    using namespace hm;
-    const V3 center = of(c->center), target = of(c->target), up = of(c->up);
-    const float fd = distance(center, target);
-    const float theta = c->fov * PI / 180.0f;
-    const float vw = 2.0f * std::tan(theta / 2.0f) * fd;
-    const float vh = vw / ((float)w * 1.0f / (float)h);
-    const V3 W = unit(target - center);
-    const V3 U = unit(cross(W, up));
-    const V3 V = unit(cross(U, W));
-    const V3 vx = U * vw, vy = V * vh;
-    const V3 dx = vx / (float)w, dy = vy / (float)h;
-    const V3 vorg = center + W * fd - vx * 0.5f - vy * 0.5f;
-    const V3 po = vorg + dx * 0.5f + dy * 0.5f;
-    CameraGPU &g = s->cam;
-    for (int a = 0; a < 3; a++) {
-        g.pixel_origin[a] = po[a]; g.dx[a] = dx[a]; g.dy[a] = dy[a]; g.center[a] = center[a];
-        g.cu[a] = U[a]; g.cv[a] = V[a]; g.background[a] = of(c->background)[a];
-    }
-    g.focus_radius = c->focus_disk_radius;
-    g.sqrt_s = (uint32_t)std::sqrt((double)c->sample_count);            // RenderPin.cu:93
-    g.recip_sqrt = 1.0f / (float)g.sqrt_s;                              // RenderPin.cu:94
-    g.depth = c->ray_trace_depth;
-    g.width = w; g.height = h;
-    g.pitch = (w + 15u) / 16u * 16u;                                    // 16x16 blocks (SDL_OpenGLWindow.cu:119-122)
+    derive_camera(c, w, h, s->cam);
     s->width = w; s->height = h;
     s->cam_ok = true;
+    return RT_OK;
+}
+
+rt_status rt_camera_reprojection(const rt_camera_input *c, uint32_t w, uint32_t h, rt_reprojection *out) {
+    if (!c || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (w == 0 || h == 0 || w > 32768 || h > 32768) return fail(RT_ERR_INVALID_ARGUMENT, "bad framebuffer size");
+    CameraGPU g{};
+    derive_camera(c, w, h, g);
+    // x = center + s (p0 + fx dx + fy dy) solved for (fx, fy, 1 / s) by Cramer's rule, in double on the camera's floats
+    double dx[3], dy[3], p0[3];
+    for (int a = 0; a < 3; a++) { dx[a] = g.dx[a]; dy[a] = g.dy[a]; p0[a] = (double)g.pixel_origin[a] - (double)g.center[a]; }
+    auto cross3 = [](const double *a, const double *b, double *r) {
+        r[0] = a[1] * b[2] - a[2] * b[1]; r[1] = a[2] * b[0] - a[0] * b[2]; r[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double rx[3], ry[3], rw[3];
+    cross3(dy, p0, rx);
+    cross3(p0, dx, ry);
+    cross3(dx, dy, rw);
+    const double det = dx[0] * rx[0] + dx[1] * rx[1] + dx[2] * rx[2];
+    rt_reprojection r;
+    bool finite = true;
+    for (int a = 0; a < 3; a++) {
+        r.centre[a] = g.center[a];
+        r.rx[a] = (float)(rx[a] / det); r.ry[a] = (float)(ry[a] / det); r.rw[a] = (float)(rw[a] / det);
+        finite = finite && std::isfinite(r.centre[a]) && std::isfinite(r.rx[a]) && std::isfinite(r.ry[a]) && std::isfinite(r.rw[a]);
+    }
+    if (!finite) return fail(RT_ERR_INVALID_ARGUMENT, "rt_camera_reprojection: the camera is degenerate (non-finite rows)");
+    *out = r;
     return RT_OK;
 }
 

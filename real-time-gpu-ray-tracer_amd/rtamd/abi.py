@@ -39,6 +39,7 @@ RT_CAMERA_QUERY_NO_SYNC = 1 << 2
 RT_CAMERA_QUERY_FIRST_SAMPLE = 1 << 3
 
 RT_DENOISE_NO_SYNC = 1 << 2
+RT_ACCUMULATE_NO_SYNC = 1 << 2
 
 RT_TRI_UPDATE_NO_SYNC = 1 << 0
 RT_TRI_UPDATE_BOUNDS = 1 << 1
@@ -156,6 +157,21 @@ class DenoiseDesc(C.Structure):
                 ("scratch_device", C.c_void_p), ("scratch_bytes", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class Reprojection(C.Structure):
+    """rt_reprojection: the rows that map a world point to a camera's frame (rt_camera_reprojection)."""
+    _fields_ = [("centre", C.c_float * 3), ("rx", C.c_float * 3), ("ry", C.c_float * 3), ("rw", C.c_float * 3)]
+
+
+class AccumulateDesc(C.Structure):
+    """rt_accumulate_desc: image size, thresholds, the previous frame's rows, device buffers and stream of one
+    rt_accumulate call."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_history", C.c_float), ("normal_cos", C.c_float), ("plane_tolerance", C.c_float),
+                ("reserved1", C.c_uint32), ("prev_view", C.POINTER(Reprojection)), ("color_device", C.c_void_p),
+                ("hits_device", C.c_void_p), ("prev_hits_device", C.c_void_p), ("prev_history_device", C.c_void_p),
+                ("history_device", C.c_void_p), ("rgb32_device", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class TriangleUpdate(C.Structure):
     """rt_triangle_update: triangle range, device vertex / normal streams and stream of one
     rt_scene_update_triangles_device call."""
@@ -215,7 +231,7 @@ EXPORTED_SYMBOLS = (
     "rt_comm_unique_id", "rt_scene_attach_comm", "rt_scene_detach_comm", "rt_slab_tiles", "rt_tile_pixels",
     "rt_comm_set_timeout", "rt_camera_control_init", "rt_camera_move", "rt_clock_ns", "rt_frame_pace",
     "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device", "rt_query_camera",
-    "rt_denoise", "rt_denoise_scratch_bytes",
+    "rt_denoise", "rt_denoise_scratch_bytes", "rt_accumulate", "rt_camera_reprojection",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -251,6 +267,10 @@ def _declare(lib):
     lib.rt_denoise.restype = C.c_int
     lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
     lib.rt_denoise_scratch_bytes.restype = C.c_uint64
+    lib.rt_accumulate.argtypes = [C.c_int, P(AccumulateDesc)]
+    lib.rt_accumulate.restype = C.c_int
+    lib.rt_camera_reprojection.argtypes = [P(CameraInput), C.c_uint32, C.c_uint32, P(Reprojection)]
+    lib.rt_camera_reprojection.restype = C.c_int
     lib.rt_synchronize.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.argtypes = [C.c_void_p]
     lib.rt_scene_destroy.restype = None

@@ -29,6 +29,22 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("instance", np.uint32), ("ptype", np.u
 DENOISE_SIGMAS = (3.0, 0.1, 0.1)
 
 
+# Renderer.accumulate's default (max_history, normal_cos, plane_tolerance): the best interior point of the grid in
+# profiles/accumulate/README.md (the C2 scene at 1080p with a strafing camera, 96 frames of 1 sample per pixel, against
+# 1 024 samples).  The error still falls with a longer history, ever more slowly, and does not depend on the plane
+# tolerance while nothing in the scene moves.
+ACCUMULATE_DEFAULTS = (32.0, 0.999, 0.02)
+
+
+def reprojection(camera_input: abi.CameraInput, width: int, height: int) -> abi.Reprojection:
+    """rt_camera_reprojection: the rows that map a world point to the frame of `camera_input` at this size (host only,
+    no scene, no GPU): what Renderer.accumulate takes as prev_view when the camera has moved since the last frame."""
+    lib = abi.load_library()
+    out = abi.Reprojection()
+    abi.check(lib, lib.rt_camera_reprojection(C.byref(camera_input), int(width), int(height), C.byref(out)))
+    return out
+
+
 def hits_to_numpy(hits) -> np.ndarray:
     """The rt_hit records of Renderer.query_rays (torch uint8 [N, 48], any device) as the structured array
     Renderer.trace_rays returns."""
@@ -439,6 +455,75 @@ class Renderer:
         d.rgba8_device = rgba.data_ptr() if want_rgba else None
         d.scratch_device = scratch.data_ptr()
         abi.check(self.lib, self.lib.rt_denoise(self.device, C.byref(d)))
+        return res
+
+    def accumulate(self, rgb, hits, prev=None, *, prev_view=None, max_history: float = ACCUMULATE_DEFAULTS[0],
+                   normal_cos: float = ACCUMULATE_DEFAULTS[1], plane_tolerance: float = ACCUMULATE_DEFAULTS[2],
+                   out_rgb=None, stream=None, sync: bool = True):
+        """rt_accumulate: temporal accumulation (include/rt.h, "Temporal accumulation") on torch CUDA tensors of the
+        shapes render and query_camera produce: rgb float32 [h, w, 3] (this frame, rendered into rgb32_device) and hits
+        uint8 [h, w, 48] (query_camera(want_hits=True) of this frame), contiguous and on the scene's device.  prev: the
+        dict the last call returned (None: the first frame, every pixel restarts).  prev_view: rtamd.reprojection of the
+        last frame's camera (None: the camera has not moved).  The threshold defaults are the best point of the grid in
+        profiles/accumulate/README.md; normal_cos=-inf and plane_tolerance=inf switch a test off.  out_rgb: the float32
+        [h, w, 3] tensor to write, which may be rgb itself (None: a new one).  Returns {"history": float32 [h, w, 4]
+        (r, g, b, length), "rgb": out_rgb, "hits": hits}: pass it back as prev for the next frame, and leave its
+        tensors unchanged until that call has run.  stream: a torch.cuda.Stream or a raw hipStream_t (None = torch's
+        current stream); the outputs are allocated on it, and with sync=False the call returns after the enqueue."""
+        import torch                              # here: `import rtamd` needs no torch
+
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+
+        def checked(x, tail, dtype, name):
+            if not isinstance(x, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor")
+            if x.dtype != dtype:
+                raise ValueError(f"{name}: {dtype}, not {x.dtype}")
+            if x.device != dev:
+                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+            if x.dim() != 3 or x.shape[2] != tail:
+                raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+            return x
+
+        rgb = checked(rgb, 3, torch.float32, "rgb")
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        nhit = C.sizeof(abi.Hit)
+        named = [(hits, nhit, torch.uint8, "hits")]
+        if out_rgb is not None:
+            named.append((out_rgb, 3, torch.float32, "out_rgb"))
+        if prev is not None:
+            named += [(prev["hits"], nhit, torch.uint8, "prev hits"), (prev["history"], 4, torch.float32, "prev history")]
+        for x, tail, dtype, name in named:
+            if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
+                raise ValueError(f"{name}: {tuple(x.shape[:2])}, rgb is {(h, w)}")
+        if prev_view is not None and not isinstance(prev_view, abi.Reprojection):
+            raise ValueError("prev_view: an abi.Reprojection (rtamd.reprojection)")
+        if not isinstance(stream, torch.cuda.Stream):
+            sync = True      # a raw hipStream_t gives torch nothing to order the outputs' allocation with (as denoise)
+        d = abi.AccumulateDesc()
+        d.width, d.height = w, h
+        d.flags = 0 if sync else abi.RT_ACCUMULATE_NO_SYNC
+        d.max_history, d.normal_cos, d.plane_tolerance = float(max_history), float(normal_cos), float(plane_tolerance)
+        d.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        with ctx:                                 # made on the call's stream, as query_camera's outputs
+            history = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+            if out_rgb is None:
+                out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        res = {"history": history, "rgb": out_rgb, "hits": hits}
+        if h * w == 0:
+            return res
+        if prev_view is not None:
+            d.prev_view = C.pointer(prev_view)
+        d.color_device, d.hits_device = rgb.data_ptr(), hits.data_ptr()
+        if prev is not None:
+            d.prev_hits_device, d.prev_history_device = prev["hits"].data_ptr(), prev["history"].data_ptr()
+        d.history_device, d.rgb32_device = history.data_ptr(), out_rgb.data_ptr()
+        abi.check(self.lib, self.lib.rt_accumulate(self.device, C.byref(d)))
         return res
 
     def synchronize(self):
