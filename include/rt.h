@@ -36,7 +36,9 @@ extern "C" {
  *    (RT_TRI_UPDATE_BOUNDS arrived within 5: a flag value that was rejected before is accepted now;
  *     rt_query_camera / rt_camera_query arrived within 5: a new entry point, no existing struct changed;
  *     rt_denoise / rt_denoise_scratch_bytes / rt_denoise_desc arrived within 5 the same way;
- *     rt_accumulate / rt_accumulate_desc / rt_camera_reprojection / rt_reprojection arrived within 5 the same way) */
+ *     rt_accumulate / rt_accumulate_desc / rt_camera_reprojection / rt_reprojection arrived within 5 the same way;
+ *     rt_accumulate_moments / rt_moments_desc / rt_denoise_guided / rt_denoise_guided_scratch_bytes /
+ *     rt_denoise_guided_desc arrived within 5 the same way) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -545,8 +547,8 @@ rt_status rt_denoise(int device, const rt_denoise_desc *desc);
  *            In float32 without FMA contraction, IEEE division, no transcendental function: the float32 restatement
  *            in tests/accumulate_ref.py gives the kernel's bits.
  * Not done : instance motion is not compensated (a moved instance is caught only by the plane test, so its pixels
- *            restart); no 3 x 3 fallback search around a failed reprojection; no luminance moments and no variance
- *            guidance for rt_denoise; sky is not reused.
+ *            restart); no 3 x 3 fallback search around a failed reprojection; sky is not reused.  (Luminance moments
+ *            and the variance-guided filter: rt_accumulate_moments and rt_denoise_guided below.)
  * Outputs  : history_device (required): float4 per pixel, next frame's prev_history_device.  rgb32_device (optional):
  *            3 floats per pixel, out.rgb; it may be color_device itself (a thread reads only its own pixel's colour).
  *            Otherwise no output may overlap an input or the other output: the byte ranges are compared on the host.
@@ -583,6 +585,98 @@ typedef struct rt_accumulate_desc {
 } rt_accumulate_desc;                                 /* 96 bytes on LP64 */
 
 rt_status rt_accumulate(int device, const rt_accumulate_desc *desc);
+
+/* Variance-guided denoising, in the manner of SVGF (Schied et al. 2017): the accumulation also carries the first two
+ * moments of each pixel's luminance (rt_accumulate_moments), and rt_denoise_guided turns them into a per-pixel
+ * variance of the accumulated colour that steers the a-trous passes and is filtered along with the colour
+ * (csrc/accumulate.hip, csrc/guided.hip).  The caller states one dimensionless sigma_luminance, the same for every
+ * frame and every pixel, where rt_denoise's sigma_color has to follow the noise level by hand.
+ *
+ * rt_accumulate_moments does all of rt_accumulate(device, desc): the same argument checks, ordering, NO_SYNC flag and
+ * outputs; history_device and rgb32_device receive, bit for bit, what rt_accumulate writes (one kernel, instantiated
+ * with and without the moments).  The same kernel accumulates the moments with the same taps, the same validity and
+ * the same weights b.  Per pixel, in float32 without FMA contraction:
+ *              a = max(albedo, 1e-3) per channel, 1 without albedo (rt_denoise's a(p));  L = lum(c / a) with
+ *              lum(r, g, b) = (0.2126f r + 0.7152f g) + 0.0722f b.
+ *              Wherever rt_accumulate resets the pixel: moments[k] = (L, L L).
+ *              Otherwise S1 = sum b M(q).x and S2 = sum b M(q).y over the valid taps (M = prev_moments), from 0 in tap
+ *              order, each product rounded before it is added; M1 = S1 / D, M2 = S2 / D;
+ *              moments[k] = (M1 + a_N (L - M1), M2 + a_N (L L - M2)) with the call's own a_N = 1 / N.
+ *            The float32 restatement in tests/guided_ref.py gives the kernel's bits.
+ * Errors   : rt_accumulate's, and before anything is enqueued (the first six answer without a GPU):
+ *            RT_ERR_INVALID_ARGUMENT for a NULL moments, reserved != 0, a NULL moments_device, prev_moments_device
+ *            present without prev_history_device or the reverse, a moments buffer not 8-byte aligned or an albedo not
+ *            4-byte aligned, a moments_device that overlaps any input or either other output; then for a buffer that
+ *            is not accessible from the device.  width * height == 0 returns RT_OK and touches no device.
+ *
+ * rt_denoise_guided filters what rt_accumulate_moments wrote.  miss, n, x, a, h (the B3 kernel), the taps and their
+ * order are rt_denoise's.  Per pixel p: N = history.w (at least 1, as rt_accumulate writes it), (m1, m2) = moments,
+ * c_0 = history.rgb / a.
+ * Variance : v_t = max(0, m2 - m1 m1), the temporal estimate.  Where N < 4 it is not trusted and a spatial one
+ *            replaces it, over the 7 x 7 window q = p + (dx, dy), dx, dy in -3 .. 3, taps outside the image left out,
+ *            summed over dy, then dx, ascending: g(p, q) = 0 when miss(p) != miss(q), else
+ *            exp(-(|n(p) - n(q)|^2 / sigma_normal^2 + (n(p) . (x(q) - x(p)))^2 / sigma_plane^2)), 1 at the centre;
+ *            v_s = max(0, sum g m2(q) / sum g - (sum g m1(q) / sum g)^2).
+ *            v_0 = (N >= 4 ? v_t : v_s) / N: the moments estimate the variance of one sample, and the accumulated
+ *            colour is a mean of about N of them.  At the history cap the blend is exponential and the true factor
+ *            is 1 / (2 max_history - 1), so dividing by N there overstates the variance by up to 2: the conservative
+ *            side (the filter trusts the colour less, never more, than it should).
+ * Filter   : pass i = 0 .. iterations - 1 has step s = 2^i.
+ *              vbar_i(p) = the 3 x 3 Gaussian, kernel (1/4, 1/2, 1/4) per axis, of v_i over the neighbours at distance
+ *              1 (at every step, not s), taps outside the image left out, summed over dy, then dx, ascending, and
+ *              divided by the sum of the kernel weights that are in.
+ *              k(p) = 1 / (sigma_luminance sqrtf(vbar_i(p)) + 1e-6f), 0 when sigma_luminance is +inf;  l_i = lum(c_i).
+ *              w(p, q) = 0 when miss(p) != miss(q), else
+ *              exp(-((|l_i(p) - l_i(q)| k(p) + |n(p) - n(q)|^2 / sigma_normal^2)
+ *                    + (n(p) . (x(q) - x(p)))^2 / sigma_plane^2));  the centre tap has w = 1.
+ *              c_{i+1}(p) = sum h w c_i(q) / sum h w;   v_{i+1}(p) = sum h^2 w^2 v_i(q) / (sum h w)^2.
+ *            sigma_luminance is not halved per pass: the variance shrinks by being filtered.  The result is
+ *            c_iterations a.  In float32 without FMA contraction; the terms of sigma_normal and sigma_plane are
+ *            multiplied by 1 / sigma^2, computed once and capped at FLT_MAX, as rt_denoise's.
+ * Outputs  : at least one of rgb32_device and rgba8_device, written as rt_denoise writes them.  variance_device
+ *            (optional): v_0, 1 float per pixel.  No output may overlap an input, another output or the scratch.
+ * Scratch  : as rt_denoise: rt_denoise_guided_scratch_bytes(width, height) bytes (64 per pixel), 16-byte aligned.
+ * Ordering : as rt_denoise; everything goes on `stream`, and the call allocates nothing.
+ * Errors   : all before anything is enqueued, the argument checks first (they answer without a GPU):
+ *            RT_ERR_INVALID_ARGUMENT for a NULL desc, reserved != 0, unknown flags, iterations outside 1..5, a sigma
+ *            that is not > 0 (NaN included), width or height above 16384, no output buffer, a NULL history_device,
+ *            moments_device, hits_device or scratch_device, scratch_bytes too small, a scratch or history not 16-byte
+ *            aligned, moments not 8-byte aligned, another buffer not 4-byte aligned, overlapping buffers as above;
+ *            then for no such device, or a buffer that is not accessible from it.  width * height == 0 with otherwise
+ *            valid arguments returns RT_OK and touches no device.  The caller's current device is preserved.
+ * Not done : the filtered colour of the first pass is not fed back as history (SVGF does); moving instances are not
+ *            compensated (as rt_accumulate); the colour accumulates modulated while the moments are demodulated, so
+ *            where the albedo changes under a kept pixel the two disagree for up to max_history frames. */
+typedef struct rt_moments_desc {
+    const float *albedo_device;        /* optional, 3 floats per pixel: the albedo the guided filter will be given */
+    const float *prev_moments_device;  /* last call's moments_device; NULL exactly when desc->prev_history_device is NULL */
+    float       *moments_device;       /* required output: float2 {m1, m2} per pixel, 8-byte aligned */
+    uint64_t     reserved;             /* 0 */
+} rt_moments_desc;                     /* 32 bytes on LP64 */
+
+rt_status rt_accumulate_moments(int device, const rt_accumulate_desc *desc, const rt_moments_desc *moments);
+
+typedef struct rt_denoise_guided_desc {
+    uint32_t width, height;          /* each <= 16384 */
+    uint32_t iterations;             /* 1..5 */
+    uint32_t flags;                  /* RT_DENOISE_NO_SYNC */
+    float sigma_luminance;           /* > 0, dimensionless (in standard deviations); +inf switches the term off */
+    float sigma_normal, sigma_plane; /* as rt_denoise */
+    uint32_t reserved;               /* 0 */
+    const float  *history_device;    /* float4 {r, g, b, length}: rt_accumulate_moments' history_device, 16-byte aligned */
+    const float  *moments_device;    /* float2 {m1, m2}: its moments_device, 8-byte aligned */
+    const rt_hit *hits_device;       /* this frame's records */
+    const float  *albedo_device;     /* optional; the one given to rt_accumulate_moments */
+    float  *rgb32_device;            /* optional output, 3 floats per pixel */
+    void   *rgba8_device;            /* optional output, as rt_denoise's */
+    float  *variance_device;         /* optional output, 1 float per pixel: v_0 */
+    void   *scratch_device;          /* >= rt_denoise_guided_scratch_bytes(width, height) bytes, 16-byte aligned */
+    uint64_t scratch_bytes;
+    void   *stream;                  /* hipStream_t; NULL = the device's null stream */
+} rt_denoise_guided_desc;            /* 112 bytes on LP64 */
+
+uint64_t  rt_denoise_guided_scratch_bytes(uint32_t width, uint32_t height);
+rt_status rt_denoise_guided(int device, const rt_denoise_guided_desc *desc);
 
 /* The box decisions of the trace kernels on caller data, for parity tests (no scene needed): box i =
  * {xmin, xmax, ymin, ymax, zmin, zmax} (6 floats), ray i = origin xyz, direction xyz, range [0.001, tmax[i]].

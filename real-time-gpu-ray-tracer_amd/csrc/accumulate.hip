@@ -14,6 +14,10 @@
 //   Measured on C2's frames (profiles/accumulate/README.md): rows is 7 to 8 % faster with a still camera, and the two
 //   tie within 0.6 % when it moves, so rows is the default.
 // Every tap's coordinates are tested before its loads; pixel indices are size_t.
+//   rt_accumulate_moments is the same function with MOMENTS = true: the same taps, validity and weights also carry
+//   the first two moments of the demodulated luminance (include/rt.h, "Variance-guided denoising"): 12 B of albedo and
+//   up to four float2 read, one float2 written.  MOMENTS = false compiles to what it was before the template
+//   (profiles/guided/kernel_resources.txt: 33 VGPRs, as profiles/accumulate/kernel_resources.txt).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -30,10 +34,24 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
     return (ax * bx + ay * by) + az * bz;
 }
 
+template <bool MOMENTS>
 __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, int j) {
     const size_t k = (size_t)j * g.w + (size_t)i;
     const float cr = g.color[3 * k + 0], cg = g.color[3 * k + 1], cb = g.color[3 * k + 2];
     float4 out = make_float4(cr, cg, cb, 1.0f);                       // reset(p)
+    float lum = 0.0f, lum2 = 0.0f;
+    float2 mom = make_float2(0.0f, 0.0f);
+    if (MOMENTS) {                                                    // L = lum(c / a), reset: (L, L L)
+        float lr = cr, lg = cg, lb = cb;
+        if (g.albedo) {
+            lr = cr / fmaxf(g.albedo[3 * k + 0], 1e-3f);
+            lg = cg / fmaxf(g.albedo[3 * k + 1], 1e-3f);
+            lb = cb / fmaxf(g.albedo[3 * k + 2], 1e-3f);
+        }
+        lum = (0.2126f * lr + 0.7152f * lg) + 0.0722f * lb;
+        lum2 = lum * lum;
+        mom = make_float2(lum, lum2);
+    }
     const rt_hit *rec = g.hits + k;
     const uint32_t inst = rec->instance;
     if (g.prev_history && inst != ACC_MISS) {
@@ -58,7 +76,7 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, 
             }
         }
         if (ok) {
-            float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, den = 0.0f;
+            float sr = 0.0f, sg = 0.0f, sb = 0.0f, sw = 0.0f, den = 0.0f, s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
             for (int tap = 0; tap < 4; tap++) {
                 const int tx = tap & 1, ty = tap >> 1;
@@ -78,16 +96,26 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, 
                 sb = sb + b * hq.z;
                 sw = sw + b * hq.w;
                 den = den + b;
+                if (MOMENTS) {
+                    const float2 mq = g.prev_moments[q];
+                    s1 = s1 + b * mq.x;
+                    s2 = s2 + b * mq.y;
+                }
             }
             if (den > 0.0f) {
                 const float hr = sr / den, hg = sg / den, hb = sb / den, hw = sw / den;
                 const float n = fminf(hw + 1.0f, g.max_history);
                 const float a = 1.0f / n;
                 out = make_float4(hr + a * (cr - hr), hg + a * (cg - hg), hb + a * (cb - hb), n);
+                if (MOMENTS) {
+                    const float m1 = s1 / den, m2 = s2 / den;
+                    mom = make_float2(m1 + a * (lum - m1), m2 + a * (lum2 - m2));
+                }
             }
         }
     }
     g.history[k] = out;
+    if (MOMENTS) g.moments[k] = mom;
     if (g.rgb) {
         g.rgb[3 * k + 0] = out.x;
         g.rgb[3 * k + 1] = out.y;
@@ -96,19 +124,21 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, 
 }
 
 // blockDim (64, 4): a wave is 64 consecutive pixels of one row
+template <bool MOMENTS>
 __global__ __launch_bounds__(256) void accumulate_rows_kernel(AccumulateGPU g) {
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     if (x >= (int)g.w || y >= (int)g.h) return;
-    accumulate_pixel(g, x, y);
+    accumulate_pixel<MOMENTS>(g, x, y);
 }
 
 // blockDim 256, a 16 x 16 tile: wave w is the 8 x 8 block (w & 1, w >> 1) of it, lane l its pixel (l & 7, l >> 3)
+template <bool MOMENTS>
 __global__ __launch_bounds__(256) void accumulate_blocks_kernel(AccumulateGPU g) {
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const int x = (int)(blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u));
     const int y = (int)(blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3));
     if (x >= (int)g.w || y >= (int)g.h) return;
-    accumulate_pixel(g, x, y);
+    accumulate_pixel<MOMENTS>(g, x, y);
 }
 
 // The mapping: 'r' rows, 'b' blocks.  scripts/accumulate_bench.py measures them side by side, alternating in one
@@ -122,11 +152,15 @@ char pixel_mapping() {
 
 }  // namespace
 
+// g.moments set: rt_accumulate_moments' instantiation
 hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream) {
-    if (pixel_mapping() == 'r')
-        hipLaunchKernelGGL(accumulate_rows_kernel, dim3((g.w + 63u) / 64u, (g.h + 3u) / 4u), dim3(64, 4), 0, stream, g);
+    const bool rows = pixel_mapping() == 'r';
+    const dim3 grid = rows ? dim3((g.w + 63u) / 64u, (g.h + 3u) / 4u) : dim3((g.w + 15u) / 16u, (g.h + 15u) / 16u);
+    const dim3 block = rows ? dim3(64, 4) : dim3(256);
+    if (g.moments)
+        hipLaunchKernelGGL(rows ? accumulate_rows_kernel<true> : accumulate_blocks_kernel<true>, grid, block, 0, stream, g);
     else
-        hipLaunchKernelGGL(accumulate_blocks_kernel, dim3((g.w + 15u) / 16u, (g.h + 15u) / 16u), dim3(256), 0, stream, g);
+        hipLaunchKernelGGL(rows ? accumulate_rows_kernel<false> : accumulate_blocks_kernel<false>, grid, block, 0, stream, g);
     return hipGetLastError();
 }
 

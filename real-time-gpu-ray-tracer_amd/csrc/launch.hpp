@@ -1,5 +1,5 @@
 // launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
-// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, denoise.hip, accumulate.hip) and the host files that call them
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, denoise.hip, accumulate.hip, guided.hip) and the host files that call them
 // include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
 #pragma once
 
@@ -86,9 +86,30 @@ struct AccumulateGPU {
     float max_history, normal_cos, plane_tolerance;
     uint32_t has_view;                 // 0: every pixel looks at itself and `view` is not read
     rt_reprojection view;
+    // rt_accumulate_moments only (moments set): the albedo is optional, prev_moments goes with prev_history
+    const float *albedo;
+    const float2 *prev_moments;
+    float2 *moments;
 };
 // one launch, one thread per pixel
 hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream);
+// guided.hip (rt_denoise_guided): the caller's buffers and the four planes of its scratch, as DenoiseGPU's; the colour
+// planes' .w lane carries the variance
+struct GuidedGPU {
+    const float4 *history;             // {r, g, b, length}
+    const float2 *moments;
+    const rt_hit *hits;
+    const float *albedo;               // optional
+    float *rgb;                        // optional output
+    uint32_t *rgba;                    // optional output
+    float *variance;                   // optional output: v_0
+    float4 *plane[2];
+    float4 *g0, *g1;
+    uint32_t w, h;
+};
+// the pack and variance passes and `iterations` (1..5) filter passes, the last one writing the outputs
+hipError_t launch_denoise_guided(const GuidedGPU &g, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                                 float sigma_plane, hipStream_t stream);
 
 // One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
 struct TraceFlavour {

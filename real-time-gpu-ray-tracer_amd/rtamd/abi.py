@@ -172,6 +172,23 @@ class AccumulateDesc(C.Structure):
                 ("history_device", C.c_void_p), ("rgb32_device", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class MomentsDesc(C.Structure):
+    """rt_moments_desc: what rt_accumulate_moments takes beside rt_accumulate's description."""
+    _fields_ = [("albedo_device", C.c_void_p), ("prev_moments_device", C.c_void_p), ("moments_device", C.c_void_p),
+                ("reserved", C.c_uint64)]
+
+
+class DenoiseGuidedDesc(C.Structure):
+    """rt_denoise_guided_desc: image size, passes, sigmas, device buffers, scratch and stream of one rt_denoise_guided
+    call."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("reserved", C.c_uint32), ("history_device", C.c_void_p), ("moments_device", C.c_void_p),
+                ("hits_device", C.c_void_p), ("albedo_device", C.c_void_p), ("rgb32_device", C.c_void_p),
+                ("rgba8_device", C.c_void_p), ("variance_device", C.c_void_p), ("scratch_device", C.c_void_p),
+                ("scratch_bytes", C.c_uint64), ("stream", C.c_void_p)]
+
+
 class TriangleUpdate(C.Structure):
     """rt_triangle_update: triangle range, device vertex / normal streams and stream of one
     rt_scene_update_triangles_device call."""
@@ -232,6 +249,7 @@ EXPORTED_SYMBOLS = (
     "rt_comm_set_timeout", "rt_camera_control_init", "rt_camera_move", "rt_clock_ns", "rt_frame_pace",
     "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device", "rt_query_camera",
     "rt_denoise", "rt_denoise_scratch_bytes", "rt_accumulate", "rt_camera_reprojection",
+    "rt_accumulate_moments", "rt_denoise_guided", "rt_denoise_guided_scratch_bytes",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -269,6 +287,12 @@ def _declare(lib):
     lib.rt_denoise_scratch_bytes.restype = C.c_uint64
     lib.rt_accumulate.argtypes = [C.c_int, P(AccumulateDesc)]
     lib.rt_accumulate.restype = C.c_int
+    lib.rt_accumulate_moments.argtypes = [C.c_int, P(AccumulateDesc), P(MomentsDesc)]
+    lib.rt_accumulate_moments.restype = C.c_int
+    lib.rt_denoise_guided.argtypes = [C.c_int, P(DenoiseGuidedDesc)]
+    lib.rt_denoise_guided.restype = C.c_int
+    lib.rt_denoise_guided_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+    lib.rt_denoise_guided_scratch_bytes.restype = C.c_uint64
     lib.rt_camera_reprojection.argtypes = [P(CameraInput), C.c_uint32, C.c_uint32, P(Reprojection)]
     lib.rt_camera_reprojection.restype = C.c_int
     lib.rt_synchronize.argtypes = [C.c_void_p]

@@ -29,6 +29,14 @@ HIT_DTYPE = np.dtype([("t", np.float32), ("instance", np.uint32), ("ptype", np.u
 DENOISE_SIGMAS = (3.0, 0.1, 0.1)
 
 
+# Renderer.denoise_guided's default (sigma_luminance, sigma_normal, sigma_plane): the best point, an interior one, of
+# the grid in profiles/guided/README.md (the C2 scene at 1080p, 64 accumulated one-sample frames from a still and a
+# strafing camera, against 1 024 samples).  sigma_luminance is dimensionless, in standard deviations of the accumulated
+# colour's luminance, and the same for every frame: the score stays within 1.4 % of the best from 2 to 16.
+# sigma_plane was not varied: rt_denoise's grid found it flat on this scene, and its 0.1 world units are kept.
+GUIDED_SIGMAS = (4.0, 0.1, 0.1)
+
+
 # Renderer.accumulate's default (max_history, normal_cos, plane_tolerance): the best interior point of the grid in
 # profiles/accumulate/README.md (the C2 scene at 1080p with a strafing camera, 96 frames of 1 sample per pixel, against
 # 1 024 samples).  The error still falls with a longer history, ever more slowly, and does not depend on the plane
@@ -459,7 +467,7 @@ class Renderer:
 
     def accumulate(self, rgb, hits, prev=None, *, prev_view=None, max_history: float = ACCUMULATE_DEFAULTS[0],
                    normal_cos: float = ACCUMULATE_DEFAULTS[1], plane_tolerance: float = ACCUMULATE_DEFAULTS[2],
-                   out_rgb=None, stream=None, sync: bool = True):
+                   out_rgb=None, stream=None, sync: bool = True, albedo=None, moments: bool = False):
         """rt_accumulate: temporal accumulation (include/rt.h, "Temporal accumulation") on torch CUDA tensors of the
         shapes render and query_camera produce: rgb float32 [h, w, 3] (this frame, rendered into rgb32_device) and hits
         uint8 [h, w, 48] (query_camera(want_hits=True) of this frame), contiguous and on the scene's device.  prev: the
@@ -469,7 +477,10 @@ class Renderer:
         [h, w, 3] tensor to write, which may be rgb itself (None: a new one).  Returns {"history": float32 [h, w, 4]
         (r, g, b, length), "rgb": out_rgb, "hits": hits}: pass it back as prev for the next frame, and leave its
         tensors unchanged until that call has run.  stream: a torch.cuda.Stream or a raw hipStream_t (None = torch's
-        current stream); the outputs are allocated on it, and with sync=False the call returns after the enqueue."""
+        current stream); the outputs are allocated on it, and with sync=False the call returns after the enqueue.
+        moments=True is rt_accumulate_moments (include/rt.h, "Variance-guided denoising"): the same history and rgb, and
+        the dict also holds "moments", float32 [h, w, 2], the first two moments of the luminance of rgb / albedo (albedo:
+        float32 [h, w, 3], optional, the one denoise_guided will be given); prev must then be a dict of such a call."""
         import torch                              # here: `import rtamd` needs no torch
 
         dev = torch.device("cuda", self.device)
@@ -498,6 +509,15 @@ class Renderer:
             named.append((out_rgb, 3, torch.float32, "out_rgb"))
         if prev is not None:
             named += [(prev["hits"], nhit, torch.uint8, "prev hits"), (prev["history"], 4, torch.float32, "prev history")]
+        if albedo is not None and not moments:
+            raise ValueError("albedo: only the moments read it (moments=True)")
+        if moments:
+            if prev is not None and "moments" not in prev:
+                raise ValueError("prev: it holds no moments (the last call had moments=False)")
+            if prev is not None:
+                named.append((prev["moments"], 2, torch.float32, "prev moments"))
+            if albedo is not None:
+                named.append((albedo, 3, torch.float32, "albedo"))
         for x, tail, dtype, name in named:
             if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
                 raise ValueError(f"{name}: {tuple(x.shape[:2])}, rgb is {(h, w)}")
@@ -514,7 +534,10 @@ class Renderer:
             history = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
             if out_rgb is None:
                 out_rgb = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+            mom = torch.empty((h, w, 2), dtype=torch.float32, device=dev) if moments else None
         res = {"history": history, "rgb": out_rgb, "hits": hits}
+        if moments:
+            res["moments"] = mom
         if h * w == 0:
             return res
         if prev_view is not None:
@@ -523,7 +546,83 @@ class Renderer:
         if prev is not None:
             d.prev_hits_device, d.prev_history_device = prev["hits"].data_ptr(), prev["history"].data_ptr()
         d.history_device, d.rgb32_device = history.data_ptr(), out_rgb.data_ptr()
-        abi.check(self.lib, self.lib.rt_accumulate(self.device, C.byref(d)))
+        if not moments:
+            abi.check(self.lib, self.lib.rt_accumulate(self.device, C.byref(d)))
+            return res
+        m = abi.MomentsDesc()
+        m.albedo_device = albedo.data_ptr() if albedo is not None else None
+        m.prev_moments_device = prev["moments"].data_ptr() if prev is not None else None
+        m.moments_device = mom.data_ptr()
+        abi.check(self.lib, self.lib.rt_accumulate_moments(self.device, C.byref(d), C.byref(m)))
+        return res
+
+    def denoise_guided(self, acc, albedo=None, *, iterations: int = 5, sigma_luminance: float = GUIDED_SIGMAS[0],
+                       sigma_normal: float = GUIDED_SIGMAS[1], sigma_plane: float = GUIDED_SIGMAS[2],
+                       want_rgba: bool = False, want_variance: bool = False, out=None, stream=None, sync: bool = True):
+        """rt_denoise_guided: the variance-steered a-trous filter (include/rt.h, "Variance-guided denoising") on the
+        dict accumulate(..., moments=True) returned: its history, moments and hits, and optionally the albedo that call
+        was given.  sigma_luminance is dimensionless and needs no scaling per frame; float("inf") switches a term off.
+        out: the float32 [h, w, 3] tensor to write (None: a new one).  Returns {"rgb": out} and, with want_rgba, "rgba"
+        uint8 [h, w, 4]; with want_variance, "variance" float32 [h, w], the variance of the accumulated luminance the
+        first pass starts from.  stream and sync as denoise."""
+        import torch                              # here: `import rtamd` needs no torch
+
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+
+        def checked(x, tail, dtype, name):
+            if not isinstance(x, torch.Tensor):
+                raise ValueError(f"{name}: a torch tensor")
+            if x.dtype != dtype:
+                raise ValueError(f"{name}: {dtype}, not {x.dtype}")
+            if x.device != dev:
+                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+            if x.dim() != 3 or x.shape[2] != tail:
+                raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
+            if not x.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+            return x
+
+        if not isinstance(acc, dict) or "moments" not in acc:
+            raise ValueError("acc: the dict accumulate(..., moments=True) returned")
+        history = checked(acc["history"], 4, torch.float32, "history")
+        h, w = int(history.shape[0]), int(history.shape[1])
+        for x, tail, dtype, name in ((acc["moments"], 2, torch.float32, "moments"),
+                                     (acc["hits"], C.sizeof(abi.Hit), torch.uint8, "hits"),
+                                     (albedo, 3, torch.float32, "albedo"), (out, 3, torch.float32, "out")):
+            if x is not None or name in ("moments", "hits"):
+                if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
+                    raise ValueError(f"{name}: {tuple(x.shape[:2])}, the history is {(h, w)}")
+        if not isinstance(stream, torch.cuda.Stream):
+            sync = True      # a raw hipStream_t gives torch nothing to order the scratch's release with (as denoise)
+        d = abi.DenoiseGuidedDesc()
+        d.width, d.height, d.iterations = w, h, int(iterations)
+        d.flags = 0 if sync else abi.RT_DENOISE_NO_SYNC
+        d.sigma_luminance, d.sigma_normal, d.sigma_plane = float(sigma_luminance), float(sigma_normal), float(sigma_plane)
+        d.scratch_bytes = self.lib.rt_denoise_guided_scratch_bytes(w, h)
+        d.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        with ctx:                                 # made on the call's stream, as query_camera's outputs
+            if out is None:
+                out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+            rgba = torch.empty((h, w, 4), dtype=torch.uint8, device=dev) if want_rgba else None
+            variance = torch.empty((h, w), dtype=torch.float32, device=dev) if want_variance else None
+            scratch = torch.empty(max(int(d.scratch_bytes), 16), dtype=torch.uint8, device=dev)
+        res = {"rgb": out}
+        if want_rgba:
+            res["rgba"] = rgba
+        if want_variance:
+            res["variance"] = variance
+        if h * w == 0:
+            return res
+        d.history_device, d.moments_device, d.hits_device = history.data_ptr(), acc["moments"].data_ptr(), acc["hits"].data_ptr()
+        d.albedo_device = albedo.data_ptr() if albedo is not None else None
+        d.rgb32_device = out.data_ptr()
+        d.rgba8_device = rgba.data_ptr() if want_rgba else None
+        d.variance_device = variance.data_ptr() if want_variance else None
+        d.scratch_device = scratch.data_ptr()
+        abi.check(self.lib, self.lib.rt_denoise_guided(self.device, C.byref(d)))
         return res
 
     def synchronize(self):
