@@ -561,7 +561,11 @@ rt_status rt_denoise(int device, const rt_denoise_desc *desc);
  *            history buffer not 16-byte aligned or another buffer not 4-byte aligned, overlapping buffers as above;
  *            then for no such device, or a buffer that hipPointerGetAttributes does not report as accessible from
  *            it.  width * height == 0 with otherwise valid arguments returns RT_OK and touches no device.  The
- *            caller's current device is preserved. */
+ *            caller's current device is preserved.  A non-finite colour or history texel is not detected: it reaches
+ *            every pixel that has it among its valid taps, a tap of weight 0 included (0 * inf is a NaN in S), and it
+ *            stays in the history until that pixel resets.  The window on fx and fy decides no result by itself (at
+ *            fx = -1 the one inside tap has weight 0 and at fx = W no tap is inside, so D = 0 either way); it keeps
+ *            values that no int holds, 1e30 or a NaN, from the conversion. */
 typedef struct rt_reprojection { float centre[3], rx[3], ry[3], rw[3]; } rt_reprojection;   /* 48 bytes */
 
 rt_status rt_camera_reprojection(const rt_camera_input *camera, uint32_t width, uint32_t height, rt_reprojection *out);
@@ -644,6 +648,10 @@ rt_status rt_accumulate(int device, const rt_accumulate_desc *desc);
  *            aligned, moments not 8-byte aligned, another buffer not 4-byte aligned, overlapping buffers as above;
  *            then for no such device, or a buffer that is not accessible from it.  width * height == 0 with otherwise
  *            valid arguments returns RT_OK and touches no device.  The caller's current device is preserved.
+ *            Non-finite history colours are not detected: a NaN or infinity spreads to the pixels whose taps reach it,
+ *            the box |dx|, |dy| <= 2 (2^iterations - 1) around it, across the hit / sky boundary too (0 * NaN), and
+ *            to no other pixel; v_0 reads no colour and is unaffected.  Non-finite moments are not detected either
+ *            and their effect is unspecified (an infinite variance gives k(p) = 0 and a finite result).
  * Not done : the filtered colour of the first pass is not fed back as history (SVGF does); moving instances are not
  *            compensated (as rt_accumulate); the colour accumulates modulated while the moments are demodulated, so
  *            where the albedo changes under a kept pixel the two disagree for up to max_history frames. */

@@ -256,9 +256,11 @@ def guided(history, moments, normal, point, miss, albedo=None, *, iterations, si
 
 def synth(width, height, seed=0, lengths="mixed"):
     """An accumulated frame on denoise_ref.synth's guides.  Lengths N from LENGTHS indexed by (x // 3 + 2 (y // 2)) % 6
-    ("mixed"), or 1 everywhere ("first": a first frame); 1 on misses either way.  Per pixel N samples, each a smooth
-    truth x (1 + amp U(-1, 1)) per channel with amp 0.5 on hits and 0.02 on sky, times the albedo; the history is
-    their mean and their count, the moments the means of lum(sample / a) and its square — with and without albedo,
+    ("mixed"), or 1 everywhere ("first": a first frame); 1 on misses either way.  `lengths` may also be a tuple of
+    ((x, y), (samples, length)) pairs (tests/filter_edges_ref.py): 8 samples and length 8.0 everywhere, misses
+    included, except at those pixels, whose stored length need not be their sample count.  Per pixel N samples, each a
+    smooth truth x (1 + amp U(-1, 1)) per channel with amp 0.5 on hits and 0.02 on sky, times the albedo; the history
+    is their mean and their length, the moments the means of lum(sample / a) and its square — with and without albedo,
     since the moments are of the demodulated luminance.  float32."""
     g = dict(D.synth(width, height, seed))
     W, H = width, height
@@ -267,13 +269,18 @@ def synth(width, height, seed=0, lengths="mixed"):
     miss = g["miss"]
     N = np.asarray(LENGTHS)[((xx.astype(int) // 3) + 2 * (yy.astype(int) // 2)) % 6] if lengths == "mixed" else np.ones((H, W), int)
     N = np.where(miss, 1, N)
+    length = N.astype(np.float64)
+    if isinstance(lengths, tuple):
+        N, length = np.full((H, W), 8), np.full((H, W), 8.0)
+        for (x, y), (count, stored) in lengths:
+            N[y, x], length[y, x] = count, stored
     truth = np.stack([0.55 + 0.35 * np.sin(0.11 * xx + 0.7 * ch) * np.cos(0.13 * yy - 0.4 * ch) for ch in range(3)], axis=-1)
     amp = np.where(miss, AMP_SKY, AMP_HIT)[None, ..., None]
     u = rng.uniform(-1.0, 1.0, (max(LENGTHS), H, W, 3))
     samples = (g["albedo"].astype(np.float64) * truth * (1.0 + amp * u)).astype(F32)
     use = (np.arange(max(LENGTHS))[:, None, None] < N[None])[..., None]
     mean = (samples.astype(np.float64) * use).sum(axis=0) / N[..., None]
-    g["history"] = np.concatenate([mean, N[..., None].astype(np.float64)], axis=-1).astype(F32)
+    g["history"] = np.concatenate([mean, length[..., None]], axis=-1).astype(F32)
     for name, alb in (("moments", g["albedo"]), ("moments_plain", None)):
         L = lum(demodulate(samples, alb, np.float64)[0], np.float64)
         m1 = (L * use[..., 0]).sum(axis=0) / N
