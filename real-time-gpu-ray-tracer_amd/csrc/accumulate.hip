@@ -22,6 +22,7 @@
 
 #include <cstdlib>
 
+#include "atrous.hpp"
 #include "launch.hpp"
 
 namespace rtamd {
@@ -43,12 +44,12 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, 
     float2 mom = make_float2(0.0f, 0.0f);
     if (MOMENTS) {                                                    // L = lum(c / a), reset: (L, L L)
         float lr = cr, lg = cg, lb = cb;
-        if (g.albedo) {
-            lr = cr / fmaxf(g.albedo[3 * k + 0], 1e-3f);
-            lg = cg / fmaxf(g.albedo[3 * k + 1], 1e-3f);
-            lb = cb / fmaxf(g.albedo[3 * k + 2], 1e-3f);
+        if (g.albedo) {                                               // as denoise.hip's and guided.hip's pack kernels divide
+            lr = cr / fmaxf(g.albedo[3 * k + 0], AT_ALBEDO_FLOOR);
+            lg = cg / fmaxf(g.albedo[3 * k + 1], AT_ALBEDO_FLOOR);
+            lb = cb / fmaxf(g.albedo[3 * k + 2], AT_ALBEDO_FLOOR);
         }
-        lum = (0.2126f * lr + 0.7152f * lg) + 0.0722f * lb;
+        lum = rtamd::lum(lr, lg, lb);
         lum2 = lum * lum;
         mom = make_float2(lum, lum2);
     }

@@ -2,20 +2,14 @@
 // include/rt.h states the filter; tests/denoise_ref.py restates it in numpy with this file's operation order.
 // Built with -ffp-contract=off: every product and sum below rounds where the reference's does, so a result differs
 // from the float32 restatement only through expf.
+// The staged tile, the staged row, the scratch planes and the leaf functions it shares with guided.hip: atrous.hpp.
 //   pack kernel     one thread per pixel: reads the colour, the albedo and the 48-byte rt_hit record once; writes the
-//                   demodulated colour (float4) and the guides — {normal, flag} and {point, 0}, a float4 plane each,
-//                   32 bytes per pixel — into scratch.  The passes read aligned 16-byte vectors only, and since no
-//                   pass reads color_device again, rgb32_device may be color_device itself.
+//                   demodulated colour (float4) and the guides, 32 bytes per pixel, into scratch.  Since no pass
+//                   reads color_device again, rgb32_device may be color_device itself.
 //   filter passes   pass i has step 2^i and ping-pongs between the two colour planes of scratch.  The last one
 //                   multiplies by the albedo again and writes rgb32 / rgba8 itself.
-//     tile form     steps 1 and 2: a 16 x 16 tile with its halo of 2 * step staged in LDS, one thread per pixel.  A tap
-//                   outside the image is staged with flag 2, which equals no pixel's flag, so its weight is 0 and the
-//                   inner loop has no coordinate test.  Rows are DN_PITCH = 32 float4 apart: ds_read_b128 serves a
-//                   wave in groups of 16 lanes that mix two tile rows (lanes {0-3, 12-15, 20-27}, ...: 8 columns of
-//                   one row and the other 8 columns of the next), and its bank is (address / 4) mod 64, so the 16
-//                   lanes cover the 64 banks exactly when the row pitch is a multiple of 16 float4.
-//     row form      steps 4, 8 and 16, where the halo reaches or exceeds the tile: 256 consecutive pixels of a row
-//                   per workgroup, one tap row staged at a time (see denoise_filter_rows_kernel).
+//     tile form     steps 1 and 2: the staged tile with its halo of 2 * step.
+//     row form      steps 4, 8 and 16, where the halo reaches or exceeds the tile: the staged row.
 //     direct form   a wave is 64 consecutive pixels of a row and reads 64 consecutive pixels at every tap: three
 //                   coalesced 1 KiB loads, from L2 / Infinity Cache after the first touch; each tap's coordinates are
 //                   tested before its loads.  Measured slower than the row form at every step (DN_FORMS), as is the
@@ -25,18 +19,14 @@
 // arithmetic, not by that traffic: about 60 VALU instructions per tap, 24 taps ("Denoiser").
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cstdlib>
 
+#include "atrous.hpp"
 #include "launch.hpp"
 
 namespace rtamd {
 
 namespace {
-
-constexpr int DN_TILE = 16;              // the LDS form's tile edge; one workgroup of 256 threads
-constexpr int DN_PITCH = 32;             // float4 per staged row (see above); the widest staged row is 16 + 4 * 4 = 32
-constexpr float DN_OUTSIDE = 2.0f;       // flag of a staged tap outside the image: hits carry 0, misses 1
 
 struct DenoisePass {
     float inv_c, inv_n, inv_p;           // 1 / sigma^2 of this pass, at most FLT_MAX; 0 for sigma = +inf
@@ -47,6 +37,7 @@ struct DenoisePass {
 struct Sums { float r, g, b, w; };
 
 // One tap: h * w(p, q) into the sums.  The flags differ for hit / miss pairs and for staged taps outside the image.
+// (dn2 and dot are also written out in guided.hip's add_tap and window_weight.)
 __device__ __forceinline__ void add_tap(const float4 &cp, const float4 &np, const float4 &xp, const float4 &cq,
                                         const float4 &nq, const float4 &xq, float h, const DenoisePass &ps, Sums &s) {
     const float dr = cp.x - cq.x, dg = cp.y - cq.y, db = cp.z - cq.z;
@@ -71,17 +62,6 @@ __device__ __forceinline__ void add_centre(const float4 &cp, float h, Sums &s) {
     s.w = s.w + h;
 }
 
-__device__ __forceinline__ float b3(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
-
-// Color3::castToUchar4 as write_pixel (shade.hpp) has it
-__device__ __forceinline__ uint32_t quantise(float r, float g, float b) {
-    const float cr = fminf(fmaxf(sqrtf(r), 0.0f), 0.999f);
-    const float cg = fminf(fmaxf(sqrtf(g), 0.0f), 0.999f);
-    const float cb = fminf(fmaxf(sqrtf(b), 0.0f), 0.999f);
-    return (uint32_t)(uint8_t)(256.0f * cr) | ((uint32_t)(uint8_t)(256.0f * cg) << 8) |
-           ((uint32_t)(uint8_t)(256.0f * cb) << 16) | (255u << 24);
-}
-
 // a pass's result for pixel i: the next plane, or (last pass) the outputs
 __device__ __forceinline__ void write_result(const DenoiseGPU &g, const DenoisePass &ps, float4 *__restrict__ dst, size_t i,
                                              const Sums &s) {
@@ -90,19 +70,7 @@ __device__ __forceinline__ void write_result(const DenoiseGPU &g, const DenoiseP
         dst[i] = make_float4(r, gr, b, 0.0f);
         return;
     }
-    float ar = 1.0f, ag = 1.0f, ab = 1.0f;
-    if (g.albedo) {
-        ar = fmaxf(g.albedo[3 * i + 0], 1e-3f);
-        ag = fmaxf(g.albedo[3 * i + 1], 1e-3f);
-        ab = fmaxf(g.albedo[3 * i + 2], 1e-3f);
-    }
-    const float o0 = r * ar, o1 = gr * ag, o2 = b * ab;
-    if (g.rgb) {
-        g.rgb[3 * i + 0] = o0;
-        g.rgb[3 * i + 1] = o1;
-        g.rgb[3 * i + 2] = o2;
-    }
-    if (g.rgba) g.rgba[i] = quantise(o0, o1, o2);
+    write_outputs(g.albedo, g.rgb, g.rgba, i, r, gr, b);
 }
 
 __global__ __launch_bounds__(256) void denoise_pack_kernel(DenoiseGPU g, float4 *__restrict__ plane) {
@@ -110,43 +78,44 @@ __global__ __launch_bounds__(256) void denoise_pack_kernel(DenoiseGPU g, float4 
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     float r = g.color[3 * i + 0], gr = g.color[3 * i + 1], b = g.color[3 * i + 2];
-    if (g.albedo) {
-        r = r / fmaxf(g.albedo[3 * i + 0], 1e-3f);
-        gr = gr / fmaxf(g.albedo[3 * i + 1], 1e-3f);
-        b = b / fmaxf(g.albedo[3 * i + 2], 1e-3f);
+    if (g.albedo) {                                          // as guided_pack_kernel and accumulate_pixel divide
+        r = r / fmaxf(g.albedo[3 * i + 0], AT_ALBEDO_FLOOR);
+        gr = gr / fmaxf(g.albedo[3 * i + 1], AT_ALBEDO_FLOOR);
+        b = b / fmaxf(g.albedo[3 * i + 2], AT_ALBEDO_FLOOR);
     }
     const rt_hit *hit = g.hits + i;
     plane[i] = make_float4(r, gr, b, 0.0f);
-    g.g0[i] = make_float4(hit->normal.x, hit->normal.y, hit->normal.z, hit->instance == 0xFFFFFFFFu ? 1.0f : 0.0f);
-    g.g1[i] = make_float4(hit->point.x, hit->point.y, hit->point.z, 0.0f);
+    g.g0[i] = guide_normal(hit);
+    g.g1[i] = guide_point(hit);
 }
 
 template <int STEP>
 __device__ __forceinline__ void filter_lds(const DenoiseGPU &g, const DenoisePass &ps, const float4 *__restrict__ src,
                                            float4 *__restrict__ dst) {
-    constexpr int HALO = 2 * STEP, EDGE = DN_TILE + 2 * HALO;
-    static_assert(EDGE <= DN_PITCH, "the staged row does not fit its pitch");
-    __shared__ float4 sc[EDGE * DN_PITCH], sn[EDGE * DN_PITCH], sx[EDGE * DN_PITCH];
-    const int x0 = (int)blockIdx.x * DN_TILE - HALO, y0 = (int)blockIdx.y * DN_TILE - HALO;
+    constexpr int HALO = 2 * STEP, EDGE = AT_TILE + 2 * HALO;
+    static_assert(EDGE <= AT_PITCH, "the staged row does not fit its pitch");
+    __shared__ float4 sc[EDGE * AT_PITCH], sn[EDGE * AT_PITCH], sx[EDGE * AT_PITCH];
+    const int x0 = (int)blockIdx.x * AT_TILE - HALO, y0 = (int)blockIdx.y * AT_TILE - HALO;
+    // the same loop stages guided.hip's filter_lds tile, and a similar one its variance tile
     for (int k = (int)threadIdx.x; k < EDGE * EDGE; k += 256) {
         const int ly = k / EDGE, lx = k - ly * EDGE;
         const int x = x0 + lx, y = y0 + ly;
-        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, DN_OUTSIDE), p = c;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, AT_OUTSIDE), p = c;
         if (x >= 0 && y >= 0 && x < (int)g.w && y < (int)g.h) {
             const size_t q = (size_t)y * g.w + (size_t)x;
             c = src[q];
             n = g.g0[q];
             p = g.g1[q];
         }
-        sc[ly * DN_PITCH + lx] = c;
-        sn[ly * DN_PITCH + lx] = n;
-        sx[ly * DN_PITCH + lx] = p;
+        sc[ly * AT_PITCH + lx] = c;
+        sn[ly * AT_PITCH + lx] = n;
+        sx[ly * AT_PITCH + lx] = p;
     }
     __syncthreads();
-    const int tx = (int)threadIdx.x % DN_TILE, ty = (int)threadIdx.x / DN_TILE;
-    const int x = (int)blockIdx.x * DN_TILE + tx, y = (int)blockIdx.y * DN_TILE + ty;
+    const int tx = (int)threadIdx.x % AT_TILE, ty = (int)threadIdx.x / AT_TILE;
+    const int x = (int)blockIdx.x * AT_TILE + tx, y = (int)blockIdx.y * AT_TILE + ty;
     if (x >= (int)g.w || y >= (int)g.h) return;
-    const int centre = (ty + HALO) * DN_PITCH + tx + HALO;
+    const int centre = (ty + HALO) * AT_PITCH + tx + HALO;
     const float4 cp = sc[centre], np = sn[centre], xp = sx[centre];
     Sums s{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -157,7 +126,7 @@ __device__ __forceinline__ void filter_lds(const DenoiseGPU &g, const DenoisePas
             if (dx == 0 && dy == 0) {
                 add_centre(cp, h, s);
             } else {
-                const int q = centre + dy * STEP * DN_PITCH + dx * STEP;
+                const int q = centre + dy * STEP * AT_PITCH + dx * STEP;
                 add_tap(cp, np, xp, sc[q], sn[q], sx[q], h, ps, s);
             }
         }
@@ -205,21 +174,13 @@ __global__ __launch_bounds__(256) void denoise_filter_direct_kernel(DenoiseGPU g
     write_result(g, ps, dst, p, s);
 }
 
-// The row form: a workgroup is DN_ROW = 256 consecutive pixels of one row.  Per tap row dy (in the image: the test is
-// block-uniform) it stages that row's DN_ROW + 4 * step pixels, then every thread takes its five dx taps from LDS: 5
-// staged rows of at most 320 pixels for 256 results, 5.6 (step 8) or 6.3 (step 16) pixel loads per result where the
-// direct form issues 25, every one of them a coalesced 16-byte load.  Two row buffers alternate, so one barrier per
-// row is enough: a buffer is overwritten two rows after its last read.  A wave reads 64 consecutive float4: no bank
-// conflict at any pitch.  The taps are summed in the order of the other forms.
-constexpr int DN_ROW = 256;
-constexpr int DN_ROW_SPAN = DN_ROW + 4 * 16;
-
+// The row form (atrous.hpp, "the staged row"); the taps are summed in the order of the other forms.
 __global__ __launch_bounds__(256) void denoise_filter_rows_kernel(DenoiseGPU g, DenoisePass ps, const float4 *__restrict__ src,
                                                                   float4 *__restrict__ dst) {
-    __shared__ float4 sc[2][DN_ROW_SPAN], sn[2][DN_ROW_SPAN], sx[2][DN_ROW_SPAN];
-    const int halo = 2 * ps.step, span = DN_ROW + 2 * halo;
-    const int x0 = (int)blockIdx.x * DN_ROW - halo, y = (int)blockIdx.y;
-    const int x = (int)blockIdx.x * DN_ROW + (int)threadIdx.x;
+    __shared__ float4 sc[2][AT_ROW_SPAN], sn[2][AT_ROW_SPAN], sx[2][AT_ROW_SPAN];
+    const int halo = 2 * ps.step, span = AT_ROW + 2 * halo;
+    const int x0 = (int)blockIdx.x * AT_ROW - halo, y = (int)blockIdx.y;
+    const int x = (int)blockIdx.x * AT_ROW + (int)threadIdx.x;
     const bool live = x < (int)g.w;
     const size_t p = (size_t)y * g.w + (size_t)(live ? x : 0);
     const float4 cp = src[p], np = g.g0[p], xp = g.g1[p];
@@ -229,19 +190,7 @@ __global__ __launch_bounds__(256) void denoise_filter_rows_kernel(DenoiseGPU g, 
     for (int dy = -2; dy <= 2; dy++) {
         const int qy = y + dy * ps.step;
         if (qy < 0 || qy >= (int)g.h) continue;            // block-uniform
-        for (int k = (int)threadIdx.x; k < span; k += DN_ROW) {
-            const int qx = x0 + k;
-            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, DN_OUTSIDE), q = c;
-            if (qx >= 0 && qx < (int)g.w) {
-                const size_t i = (size_t)qy * g.w + (size_t)qx;
-                c = src[i];
-                n = g.g0[i];
-                q = g.g1[i];
-            }
-            sc[buf][k] = c;
-            sn[buf][k] = n;
-            sx[buf][k] = q;
-        }
+        stage_row(g, src, x0, qy, span, sc[buf], sn[buf], sx[buf]);
         __syncthreads();
 #pragma unroll
         for (int dx = -2; dx <= 2; dx++) {
@@ -256,12 +205,6 @@ __global__ __launch_bounds__(256) void denoise_filter_rows_kernel(DenoiseGPU g, 
         buf ^= 1;
     }
     if (live) write_result(g, ps, dst, p, s);
-}
-
-// 1 / sigma^2 as the kernels multiply by it: 0 for +inf, and never +inf itself (0 * inf would be NaN for equal pixels)
-float inv_sq(float sigma) {
-    const float inv = 1.0f / (sigma * sigma);
-    return inv < FLT_MAX ? inv : FLT_MAX;
 }
 
 // The form of the passes of step 4, 8 and 16, one letter each: 't' the LDS tile (step 4 only: a 32 x 32 staged tile,
@@ -283,7 +226,7 @@ hipError_t launch_denoise(const DenoiseGPU &g, uint32_t iterations, float sigma_
     const size_t n = (size_t)g.w * g.h;
     hipLaunchKernelGGL(denoise_pack_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, g, g.plane[0]);
     hipError_t e = hipGetLastError();
-    const dim3 tiles((g.w + DN_TILE - 1) / DN_TILE, (g.h + DN_TILE - 1) / DN_TILE);
+    const dim3 tiles((g.w + AT_TILE - 1) / AT_TILE, (g.h + AT_TILE - 1) / AT_TILE);
     char forms[3];
     pass_forms(forms);
     for (uint32_t i = 0; i < iterations && e == hipSuccess; i++) {
@@ -303,7 +246,7 @@ hipError_t launch_denoise(const DenoiseGPU &g, uint32_t iterations, float sigma_
         else if (form == 't')
             hipLaunchKernelGGL(denoise_filter_lds4_kernel, tiles, dim3(256), 0, stream, g, ps, src, dst);
         else if (form == 'r')
-            hipLaunchKernelGGL(denoise_filter_rows_kernel, dim3((g.w + DN_ROW - 1) / DN_ROW, g.h), dim3(DN_ROW), 0, stream, g, ps,
+            hipLaunchKernelGGL(denoise_filter_rows_kernel, dim3((g.w + AT_ROW - 1) / AT_ROW, g.h), dim3(AT_ROW), 0, stream, g, ps,
                                src, dst);
         else
             hipLaunchKernelGGL(denoise_filter_direct_kernel, dim3((g.w + 63u) / 64u, (g.h + 3u) / 4u), dim3(64, 4), 0, stream,

@@ -2,43 +2,41 @@
 // colour, in the manner of SVGF (Schied et al. 2017).  include/rt.h ("Variance-guided denoising") states the filter;
 // tests/guided_ref.py restates it in numpy with this file's operation order.  Built with -ffp-contract=off: every
 // product and sum rounds where the reference's does, so a result differs from the float32 restatement only through
-// expf.
+// expf.  The staged tile, the staged row, the scratch planes and the leaf functions it shares with denoise.hip:
+// atrous.hpp.
 //   pack kernel      one thread per pixel: reads the history texel, the moments, the albedo and the rt_hit record once;
-//                    writes the demodulated colour and the guides as denoise.hip's pack kernel does.  The colour
+//                    writes the demodulated colour and the guides.  The colour
 //                    plane's .w lane, which rt_denoise leaves 0, carries the variance: v_0 = v_t / N where the history
 //                    is at least GD_MIN_LENGTH frames long, else -N, a request for the spatial estimate.
 //   variance kernel  where the pack kernel left a request, the 7 x 7 window of moments weighted by the guides; a thread
 //                    reads other pixels' guides and moments but only its own .w lane, so the kernel works in place.
 //                    On a first frame every pixel asks; in steady state only sky and disocclusions.  Two forms, the
 //                    same sums in the same order and so the same bits (GD_PREP):
-//     tile form      a 16 x 16 tile with its halo of 3 staged in LDS (guides and moments, 40 B per pixel), after a
-//                    block-wide vote: a tile without a request reads 4 bytes per pixel and leaves before staging.  A
-//                    staged tap outside the image carries GD_OUTSIDE and zero moments: weight 0, no coordinate test.
+//     tile form      the staged tile with its halo of 3 (guides and moments, 40 B per pixel), after a block-wide
+//                    vote: a tile without a request reads 4 bytes per pixel and leaves before staging.  A staged
+//                    tap outside the image carries AT_OUTSIDE and zero moments: weight 0, no coordinate test.
 //     direct form    a wave is 64 consecutive pixels of a row; direct loads under the per-pixel branch, every tap's
 //                    coordinates tested before its loads.
 //   filter passes    pass i has step 2^i and ping-pongs between the two colour planes, variance included, so a pass's
 //                    traffic stays 48 + 16 B per pixel.  The last one multiplies by the albedo and writes the outputs.
-//     tile form      steps 1 and 2: denoise.hip's 16 x 16 tile with its halo of 2 * step in LDS.  The 3 x 3 Gaussian of
-//                    the variance reads the centre's neighbours at distance 1 from the staged tile.
-//     row form       steps 4, 8 and 16: denoise.hip's 256-pixel row chunks, one tap row staged at a time.  Rows y - 1
-//                    and y + 1 are not among them, so the nine variances come from the source plane by direct loads
-//                    (4 bytes each, from lines the previous pass has just written).
+//     tile form      steps 1 and 2: the staged tile with its halo of 2 * step.  The 3 x 3 Gaussian of the variance
+//                    reads the centre's neighbours at distance 1 from it.
+//     row form       steps 4, 8 and 16: the staged row.  Rows y - 1 and y + 1 are not among the tap rows, so the nine
+//                    variances come from the source plane by direct loads (4 bytes each, from lines the previous
+//                    pass has just written).
 // Pixel indices are size_t.  No scratch memory and no spills (profiles/guided/kernel_resources.txt).
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 
+#include "atrous.hpp"
 #include "launch.hpp"
 
 namespace rtamd {
 
 namespace {
 
-constexpr int GD_TILE = 16;              // as denoise.hip's DN_TILE, DN_PITCH and DN_OUTSIDE
-constexpr int GD_PITCH = 32;
-constexpr float GD_OUTSIDE = 2.0f;
 constexpr float GD_MIN_LENGTH = 4.0f;    // shorter histories take the spatial variance estimate
 constexpr int GD_WINDOW = 3;             // its window's radius
 
@@ -52,17 +50,14 @@ struct GuidedPass {
 
 struct GuidedSums { float r, g, b, v, w; };
 
-__device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-__device__ __forceinline__ float b3(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
-
 // 1 / (sigma_luminance sqrt(vbar) + 1e-6), 0 with the term off
 __device__ __forceinline__ float lum_scale(const GuidedPass &ps, float vsum, float ksum) {
     const float vbar = vsum / ksum;
     return ps.lum_on ? 1.0f / (ps.sigma_l * sqrtf(vbar) + 1e-6f) : 0.0f;
 }
 
-// One tap: h w(p, q) into the colour sums, (h w)^2 into the variance's.  cq.w is v_i(q).
+// One tap: h w(p, q) into the colour sums, (h w)^2 into the variance's.  cq.w is v_i(q).  (dn2 and dot are also
+// written out in window_weight below and in denoise.hip's add_tap.)
 __device__ __forceinline__ void add_tap(float lp, float kp, const float4 &np, const float4 &xp, const float4 &cq,
                                         const float4 &nq, const float4 &xq, float h, const GuidedPass &ps, GuidedSums &s) {
     const float dl = fabsf(lp - lum(cq.x, cq.y, cq.z));
@@ -88,15 +83,6 @@ __device__ __forceinline__ void add_centre(const float4 &cp, float h, GuidedSums
     s.w = s.w + h;
 }
 
-// Color3::castToUchar4 as write_pixel (shade.hpp) has it
-__device__ __forceinline__ uint32_t quantise(float r, float g, float b) {
-    const float cr = fminf(fmaxf(sqrtf(r), 0.0f), 0.999f);
-    const float cg = fminf(fmaxf(sqrtf(g), 0.0f), 0.999f);
-    const float cb = fminf(fmaxf(sqrtf(b), 0.0f), 0.999f);
-    return (uint32_t)(uint8_t)(256.0f * cr) | ((uint32_t)(uint8_t)(256.0f * cg) << 8) |
-           ((uint32_t)(uint8_t)(256.0f * cb) << 16) | (255u << 24);
-}
-
 // a pass's result for pixel i: the next plane, or (last pass) the outputs
 __device__ __forceinline__ void write_result(const GuidedGPU &g, const GuidedPass &ps, float4 *__restrict__ dst, size_t i,
                                              const GuidedSums &s) {
@@ -105,19 +91,7 @@ __device__ __forceinline__ void write_result(const GuidedGPU &g, const GuidedPas
         dst[i] = make_float4(r, gr, b, s.v / (s.w * s.w));
         return;
     }
-    float ar = 1.0f, ag = 1.0f, ab = 1.0f;
-    if (g.albedo) {
-        ar = fmaxf(g.albedo[3 * i + 0], 1e-3f);
-        ag = fmaxf(g.albedo[3 * i + 1], 1e-3f);
-        ab = fmaxf(g.albedo[3 * i + 2], 1e-3f);
-    }
-    const float o0 = r * ar, o1 = gr * ag, o2 = b * ab;
-    if (g.rgb) {
-        g.rgb[3 * i + 0] = o0;
-        g.rgb[3 * i + 1] = o1;
-        g.rgb[3 * i + 2] = o2;
-    }
-    if (g.rgba) g.rgba[i] = quantise(o0, o1, o2);
+    write_outputs(g.albedo, g.rgb, g.rgba, i, r, gr, b);
 }
 
 __global__ __launch_bounds__(256) void guided_pack_kernel(GuidedGPU g) {
@@ -126,10 +100,10 @@ __global__ __launch_bounds__(256) void guided_pack_kernel(GuidedGPU g) {
     if (i >= n) return;
     const float4 hist = g.history[i];
     float r = hist.x, gr = hist.y, b = hist.z;
-    if (g.albedo) {
-        r = r / fmaxf(g.albedo[3 * i + 0], 1e-3f);
-        gr = gr / fmaxf(g.albedo[3 * i + 1], 1e-3f);
-        b = b / fmaxf(g.albedo[3 * i + 2], 1e-3f);
+    if (g.albedo) {                                          // as denoise_pack_kernel and accumulate_pixel divide
+        r = r / fmaxf(g.albedo[3 * i + 0], AT_ALBEDO_FLOOR);
+        gr = gr / fmaxf(g.albedo[3 * i + 1], AT_ALBEDO_FLOOR);
+        b = b / fmaxf(g.albedo[3 * i + 2], AT_ALBEDO_FLOOR);
     }
     const float2 m = g.moments[i];
     float v = -hist.w;                                       // the variance kernel's business
@@ -139,11 +113,11 @@ __global__ __launch_bounds__(256) void guided_pack_kernel(GuidedGPU g) {
     }
     const rt_hit *hit = g.hits + i;
     g.plane[0][i] = make_float4(r, gr, b, v);
-    g.g0[i] = make_float4(hit->normal.x, hit->normal.y, hit->normal.z, hit->instance == 0xFFFFFFFFu ? 1.0f : 0.0f);
-    g.g1[i] = make_float4(hit->point.x, hit->point.y, hit->point.z, 0.0f);
+    g.g0[i] = guide_normal(hit);
+    g.g1[i] = guide_point(hit);
 }
 
-// One window tap into the sums; the centre has w = 1
+// One window tap into the sums; the centre has w = 1.  (dn2 and dot: as add_tap has them.)
 __device__ __forceinline__ float window_weight(const float4 &np, const float4 &xp, const float4 &nq, const float4 &xq,
                                                float inv_n, float inv_p) {
     const float nx = np.x - nq.x, ny = np.y - nq.y, nz = np.z - nq.z;
@@ -156,12 +130,12 @@ __device__ __forceinline__ float window_weight(const float4 &np, const float4 &x
 
 // blockDim 256, a 16 x 16 tile, one thread per pixel
 __global__ __launch_bounds__(256) void guided_variance_tile_kernel(GuidedGPU g, float inv_n, float inv_p) {
-    constexpr int EDGE = GD_TILE + 2 * GD_WINDOW;
-    static_assert(EDGE <= GD_PITCH, "the staged row does not fit its pitch");
-    __shared__ float4 sn[EDGE * GD_PITCH], sx[EDGE * GD_PITCH];
-    __shared__ float2 sm[EDGE * GD_PITCH];
-    const int tx = (int)threadIdx.x % GD_TILE, ty = (int)threadIdx.x / GD_TILE;
-    const int x = (int)blockIdx.x * GD_TILE + tx, y = (int)blockIdx.y * GD_TILE + ty;
+    constexpr int EDGE = AT_TILE + 2 * GD_WINDOW;
+    static_assert(EDGE <= AT_PITCH, "the staged row does not fit its pitch");
+    __shared__ float4 sn[EDGE * AT_PITCH], sx[EDGE * AT_PITCH];
+    __shared__ float2 sm[EDGE * AT_PITCH];
+    const int tx = (int)threadIdx.x % AT_TILE, ty = (int)threadIdx.x / AT_TILE;
+    const int x = (int)blockIdx.x * AT_TILE + tx, y = (int)blockIdx.y * AT_TILE + ty;
     float *slot = nullptr;
     float length = 0.0f;
     if (x < (int)g.w && y < (int)g.h) {
@@ -170,11 +144,12 @@ __global__ __launch_bounds__(256) void guided_variance_tile_kernel(GuidedGPU g, 
     }
     const bool asks = length > 0.0f;                         // else the pack kernel wrote v_0 itself
     if (!__syncthreads_or(asks ? 1 : 0)) return;
-    const int x0 = (int)blockIdx.x * GD_TILE - GD_WINDOW, y0 = (int)blockIdx.y * GD_TILE - GD_WINDOW;
+    const int x0 = (int)blockIdx.x * AT_TILE - GD_WINDOW, y0 = (int)blockIdx.y * AT_TILE - GD_WINDOW;
+    // as filter_lds stages its tile, with the moments in the colour's place
     for (int k = (int)threadIdx.x; k < EDGE * EDGE; k += 256) {
         const int ly = k / EDGE, lx = k - ly * EDGE;
         const int qx = x0 + lx, qy = y0 + ly;
-        float4 n = make_float4(0.0f, 0.0f, 0.0f, GD_OUTSIDE), p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        float4 n = make_float4(0.0f, 0.0f, 0.0f, AT_OUTSIDE), p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         float2 m = make_float2(0.0f, 0.0f);
         if (qx >= 0 && qy >= 0 && qx < (int)g.w && qy < (int)g.h) {
             const size_t q = (size_t)qy * g.w + (size_t)qx;
@@ -182,19 +157,19 @@ __global__ __launch_bounds__(256) void guided_variance_tile_kernel(GuidedGPU g, 
             p = g.g1[q];
             m = g.moments[q];
         }
-        sn[ly * GD_PITCH + lx] = n;
-        sx[ly * GD_PITCH + lx] = p;
-        sm[ly * GD_PITCH + lx] = m;
+        sn[ly * AT_PITCH + lx] = n;
+        sx[ly * AT_PITCH + lx] = p;
+        sm[ly * AT_PITCH + lx] = m;
     }
     __syncthreads();
     if (!asks) return;
-    const int centre = (ty + GD_WINDOW) * GD_PITCH + tx + GD_WINDOW;
+    const int centre = (ty + GD_WINDOW) * AT_PITCH + tx + GD_WINDOW;
     const float4 np = sn[centre], xp = sx[centre];
     float sg = 0.0f, s1 = 0.0f, s2 = 0.0f;
     for (int dy = -GD_WINDOW; dy <= GD_WINDOW; dy++) {
 #pragma unroll
         for (int dx = -GD_WINDOW; dx <= GD_WINDOW; dx++) {
-            const int q = centre + dy * GD_PITCH + dx;
+            const int q = centre + dy * AT_PITCH + dx;
             const float2 m = sm[q];
             const float w = (dx == 0 && dy == 0) ? 1.0f : window_weight(np, xp, sn[q], sx[q], inv_n, inv_p);
             sg = sg + w;
@@ -202,7 +177,7 @@ __global__ __launch_bounds__(256) void guided_variance_tile_kernel(GuidedGPU g, 
             s2 = s2 + w * m.y;
         }
     }
-    const float m1 = s1 / sg, m2 = s2 / sg;
+    const float m1 = s1 / sg, m2 = s2 / sg;                  // as guided_variance_direct_kernel ends
     const float v = fmaxf(0.0f, m2 - m1 * m1) / length;
     *slot = v;
     if (g.variance) g.variance[(size_t)y * g.w + (size_t)x] = v;
@@ -232,7 +207,7 @@ __global__ __launch_bounds__(256) void guided_variance_direct_kernel(GuidedGPU g
             s2 = s2 + w * m.y;
         }
     }
-    const float m1 = s1 / sg, m2 = s2 / sg;
+    const float m1 = s1 / sg, m2 = s2 / sg;                  // as guided_variance_tile_kernel ends
     const float v = fmaxf(0.0f, m2 - m1 * m1) / length;
     *slot = v;
     if (g.variance) g.variance[p] = v;
@@ -241,39 +216,40 @@ __global__ __launch_bounds__(256) void guided_variance_direct_kernel(GuidedGPU g
 template <int STEP>
 __device__ __forceinline__ void filter_lds(const GuidedGPU &g, const GuidedPass &ps, const float4 *__restrict__ src,
                                            float4 *__restrict__ dst) {
-    constexpr int HALO = 2 * STEP, EDGE = GD_TILE + 2 * HALO;
-    static_assert(EDGE <= GD_PITCH, "the staged row does not fit its pitch");
-    __shared__ float4 sc[EDGE * GD_PITCH], sn[EDGE * GD_PITCH], sx[EDGE * GD_PITCH];
-    const int x0 = (int)blockIdx.x * GD_TILE - HALO, y0 = (int)blockIdx.y * GD_TILE - HALO;
+    constexpr int HALO = 2 * STEP, EDGE = AT_TILE + 2 * HALO;
+    static_assert(EDGE <= AT_PITCH, "the staged row does not fit its pitch");
+    __shared__ float4 sc[EDGE * AT_PITCH], sn[EDGE * AT_PITCH], sx[EDGE * AT_PITCH];
+    const int x0 = (int)blockIdx.x * AT_TILE - HALO, y0 = (int)blockIdx.y * AT_TILE - HALO;
+    // the same loop stages denoise.hip's filter_lds tile
     for (int k = (int)threadIdx.x; k < EDGE * EDGE; k += 256) {
         const int ly = k / EDGE, lx = k - ly * EDGE;
         const int x = x0 + lx, y = y0 + ly;
-        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, GD_OUTSIDE), p = c;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, AT_OUTSIDE), p = c;
         if (x >= 0 && y >= 0 && x < (int)g.w && y < (int)g.h) {
             const size_t q = (size_t)y * g.w + (size_t)x;
             c = src[q];
             n = g.g0[q];
             p = g.g1[q];
         }
-        sc[ly * GD_PITCH + lx] = c;
-        sn[ly * GD_PITCH + lx] = n;
-        sx[ly * GD_PITCH + lx] = p;
+        sc[ly * AT_PITCH + lx] = c;
+        sn[ly * AT_PITCH + lx] = n;
+        sx[ly * AT_PITCH + lx] = p;
     }
     __syncthreads();
-    const int tx = (int)threadIdx.x % GD_TILE, ty = (int)threadIdx.x / GD_TILE;
-    const int x = (int)blockIdx.x * GD_TILE + tx, y = (int)blockIdx.y * GD_TILE + ty;
+    const int tx = (int)threadIdx.x % AT_TILE, ty = (int)threadIdx.x / AT_TILE;
+    const int x = (int)blockIdx.x * AT_TILE + tx, y = (int)blockIdx.y * AT_TILE + ty;
     if (x >= (int)g.w || y >= (int)g.h) return;
-    const int centre = (ty + HALO) * GD_PITCH + tx + HALO;
+    const int centre = (ty + HALO) * AT_PITCH + tx + HALO;
     const float4 cp = sc[centre], np = sn[centre], xp = sx[centre];
-    // the 3 x 3 Gaussian of the variance, distance 1 at every step; a staged tap outside the image carries GD_OUTSIDE
+    // the 3 x 3 Gaussian of the variance, distance 1 at every step; a staged tap outside the image carries AT_OUTSIDE
     float vsum = 0.0f, ksum = 0.0f;
 #pragma unroll
     for (int dy = -1; dy <= 1; dy++) {
 #pragma unroll
         for (int dx = -1; dx <= 1; dx++) {
-            const int q = centre + dy * GD_PITCH + dx;
-            if (sn[q].w == GD_OUTSIDE) continue;
-            const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+            const int q = centre + dy * AT_PITCH + dx;
+            if (sn[q].w == AT_OUTSIDE) continue;
+            const float k = g3(dx, dy);
             vsum = vsum + k * sc[q].w;
             ksum = ksum + k;
         }
@@ -288,7 +264,7 @@ __device__ __forceinline__ void filter_lds(const GuidedGPU &g, const GuidedPass 
             if (dx == 0 && dy == 0) {
                 add_centre(cp, h, s);
             } else {
-                const int q = centre + dy * STEP * GD_PITCH + dx * STEP;
+                const int q = centre + dy * STEP * AT_PITCH + dx * STEP;
                 add_tap(lp, kp, np, xp, sc[q], sn[q], sx[q], h, ps, s);
             }
         }
@@ -305,17 +281,13 @@ __global__ __launch_bounds__(256) void guided_filter_lds2_kernel(GuidedGPU g, Gu
     filter_lds<2>(g, ps, src, dst);
 }
 
-// The row form of denoise.hip: a workgroup is GD_ROW = 256 consecutive pixels of one row, one tap row staged at a time
-// in two alternating buffers, one barrier per row.
-constexpr int GD_ROW = 256;
-constexpr int GD_ROW_SPAN = GD_ROW + 4 * 16;
-
+// The row form (atrous.hpp, "the staged row")
 __global__ __launch_bounds__(256) void guided_filter_rows_kernel(GuidedGPU g, GuidedPass ps, const float4 *__restrict__ src,
                                                                  float4 *__restrict__ dst) {
-    __shared__ float4 sc[2][GD_ROW_SPAN], sn[2][GD_ROW_SPAN], sx[2][GD_ROW_SPAN];
-    const int halo = 2 * ps.step, span = GD_ROW + 2 * halo;
-    const int x0 = (int)blockIdx.x * GD_ROW - halo, y = (int)blockIdx.y;
-    const int x = (int)blockIdx.x * GD_ROW + (int)threadIdx.x;
+    __shared__ float4 sc[2][AT_ROW_SPAN], sn[2][AT_ROW_SPAN], sx[2][AT_ROW_SPAN];
+    const int halo = 2 * ps.step, span = AT_ROW + 2 * halo;
+    const int x0 = (int)blockIdx.x * AT_ROW - halo, y = (int)blockIdx.y;
+    const int x = (int)blockIdx.x * AT_ROW + (int)threadIdx.x;
     const bool live = x < (int)g.w;
     const int xc = live ? x : 0;
     const size_t p = (size_t)y * g.w + (size_t)xc;
@@ -328,7 +300,7 @@ __global__ __launch_bounds__(256) void guided_filter_rows_kernel(GuidedGPU g, Gu
         for (int dx = -1; dx <= 1; dx++) {
             const int qx = xc + dx;
             if (qx < 0 || qy < 0 || qx >= (int)g.w || qy >= (int)g.h) continue;
-            const float k = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
+            const float k = g3(dx, dy);
             const float vq = (dx == 0 && dy == 0) ? cp.w : reinterpret_cast<const float *>(src + ((size_t)qy * g.w + (size_t)qx))[3];
             vsum = vsum + k * vq;
             ksum = ksum + k;
@@ -341,19 +313,7 @@ __global__ __launch_bounds__(256) void guided_filter_rows_kernel(GuidedGPU g, Gu
     for (int dy = -2; dy <= 2; dy++) {
         const int qy = y + dy * ps.step;
         if (qy < 0 || qy >= (int)g.h) continue;            // block-uniform
-        for (int k = (int)threadIdx.x; k < span; k += GD_ROW) {
-            const int qx = x0 + k;
-            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, GD_OUTSIDE), q = c;
-            if (qx >= 0 && qx < (int)g.w) {
-                const size_t i = (size_t)qy * g.w + (size_t)qx;
-                c = src[i];
-                n = g.g0[i];
-                q = g.g1[i];
-            }
-            sc[buf][k] = c;
-            sn[buf][k] = n;
-            sx[buf][k] = q;
-        }
+        stage_row(g, src, x0, qy, span, sc[buf], sn[buf], sx[buf]);
         __syncthreads();
 #pragma unroll
         for (int dx = -2; dx <= 2; dx++) {
@@ -368,12 +328,6 @@ __global__ __launch_bounds__(256) void guided_filter_rows_kernel(GuidedGPU g, Gu
         buf ^= 1;
     }
     if (live) write_result(g, ps, dst, p, s);
-}
-
-// 1 / sigma^2 as the kernels multiply by it: 0 for +inf, and never +inf itself (0 * inf would be NaN for equal pixels)
-float inv_sq(float sigma) {
-    const float inv = 1.0f / (sigma * sigma);
-    return inv < FLT_MAX ? inv : FLT_MAX;
 }
 
 // The variance kernel's form: 't' the LDS tile, 'd' direct.  Both give the same bits.  scripts/guided_bench.py measures
@@ -398,7 +352,7 @@ hipError_t launch_denoise_guided(const GuidedGPU &g, uint32_t iterations, float 
     hipLaunchKernelGGL(guided_pack_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, stream, g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const dim3 tiles((g.w + GD_TILE - 1) / GD_TILE, (g.h + GD_TILE - 1) / GD_TILE);
+    const dim3 tiles((g.w + AT_TILE - 1) / AT_TILE, (g.h + AT_TILE - 1) / AT_TILE);
     if (prep_form() == 't')
         hipLaunchKernelGGL(guided_variance_tile_kernel, tiles, dim3(256), 0, stream, g, ps.inv_n, ps.inv_p);
     else
@@ -415,7 +369,7 @@ hipError_t launch_denoise_guided(const GuidedGPU &g, uint32_t iterations, float 
         else if (ps.step == 2)
             hipLaunchKernelGGL(guided_filter_lds2_kernel, tiles, dim3(256), 0, stream, g, ps, src, dst);
         else
-            hipLaunchKernelGGL(guided_filter_rows_kernel, dim3((g.w + GD_ROW - 1) / GD_ROW, g.h), dim3(GD_ROW), 0, stream, g, ps,
+            hipLaunchKernelGGL(guided_filter_rows_kernel, dim3((g.w + AT_ROW - 1) / AT_ROW, g.h), dim3(AT_ROW), 0, stream, g, ps,
                                src, dst);
         e = hipGetLastError();
     }

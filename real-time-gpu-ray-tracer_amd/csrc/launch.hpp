@@ -1,5 +1,6 @@
 // launch.hpp — every host-side kernel launcher, declared once: the TUs that define them (trace_kernel.hip with
-// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, denoise.hip, accumulate.hip, guided.hip) and the host files that call them
+// ray_query.hpp in its three flavours, schedule.hip, assemble.hip, instances.hip, tri_update.hip, inst_bounds.hip, and
+// the image filters denoise.hip, accumulate.hip, guided.hip) and the host files that call them (the filters': filters.cpp)
 // include this header, so a signature that drifts fails where it was changed.  (launch_tlas_small: lbvh.hpp.)
 #pragma once
 

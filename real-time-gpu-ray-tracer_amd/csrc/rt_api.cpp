@@ -16,7 +16,9 @@
 //   blas_gpu.cpp    the GPU BLAS builds of RT_BUILD_LBVH and their segments
 //   update.cpp      rt_scene_update_triangles / _triangles_device / _instances, the device-bounds state
 //   render.cpp      rt_render with auto_lanes and order_null, rt_assemble_tiles, rt_trace_rays, rt_query_rays, rt_query_camera,
-//                   rt_box_test, rt_denoise (denoise.hip), rt_accumulate / _moments (accumulate.hip), rt_denoise_guided (guided.hip)
+//                   rt_box_test
+//   filters.cpp     the calls that take no scene: rt_denoise (denoise.hip), rt_accumulate / _moments (accumulate.hip),
+//                   rt_denoise_guided (guided.hip); select_device
 //   scene_comm.cpp  the RCCL attach / detach / abort path and a frame's gather
 //   debug.cpp       rt_scene_debug_read, rt_scene_export_blas / _tlas
 #include "scene.hpp"

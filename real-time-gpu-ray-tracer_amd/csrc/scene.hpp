@@ -1,7 +1,7 @@
 // scene.hpp — the scene's state (struct rt_scene) and the internal interface between the host files: the error and
 // wait discipline (scene_sync.cpp), the host half of a frame (frame.cpp), the acceleration-structure builds (build.cpp,
 // blas_gpu.cpp), the geometry updates (update.cpp), the RCCL path (scene_comm.cpp); render.cpp, debug.cpp and
-// rt_api.cpp only call into them.  What the scene keeps per overlap lane, per frame block and per staging buffer is
+// rt_api.cpp only call into them, and filters.cpp, whose calls take no scene, uses the error discipline alone.  What the scene keeps per overlap lane, per frame block and per staging buffer is
 // declared once each (Lane, FrameBlock, Stage), with the members that create, reset and release it.
 #pragma once
 
@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -565,10 +566,12 @@ inline bool dev_bounded_rec(const rt_scene *s, size_t record) { return !s->dev_b
 // scene_comm.cpp: a multi-GPU frame's gather to rank 0 and its assembly there, on the trace's stream
 rt_status comm_gather(rt_scene *s, int q, uint8_t *frame_out, hipStream_t stream);
 
-// rt_api.cpp, render.cpp
+// rt_api.cpp, render.cpp, filters.cpp
 uint32_t tiles_for_rank(uint32_t w, uint32_t h, uint32_t tw, uint32_t th, uint32_t rank, uint32_t count);
 void fill_stats(rt_stats *st, const unsigned long long *c);
 rt_status sum_lane_counters(rt_scene *s, unsigned long long *sum);
 bool device_accessible(const void *p, int device);
+rt_status all_accessible(std::initializer_list<const void *> bufs, int device, const std::string &message);
+rt_status select_device(int device);
 
 }  // namespace rtamd

@@ -60,6 +60,29 @@ def hits_to_numpy(hits) -> np.ndarray:
     return np.ascontiguousarray(raw).reshape(-1, HIT_DTYPE.itemsize).view(HIT_DTYPE).reshape(-1).copy()
 
 
+def _raw_stream(stream):
+    """The hipStream_t of a descriptor's stream field: of a torch stream, or the raw handle given; None for the null
+    stream."""
+    return (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+
+
+def checked(x, tail, dtype, name, dev):
+    """x as a filter call takes it: a contiguous torch tensor [h, w, tail] of dtype on the torch device dev."""
+    import torch                                  # here: `import rtamd` needs no torch
+
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{name}: a torch tensor")
+    if x.dtype != dtype:
+        raise ValueError(f"{name}: {dtype}, not {x.dtype}")
+    if x.device != dev:
+        raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
+    if x.dim() != 3 or x.shape[2] != tail:
+        raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    return x
+
+
 class Renderer:
     def __init__(self, scene, device: int = 0, update=None):
         """update: None -> the scene's own animation (Main.cu updateInstance via the native
@@ -81,6 +104,18 @@ class Renderer:
         self.h = h
         self.device = device
         self.width = self.height = 0
+
+    def _torch_call(self, stream):
+        """What a call on torch tensors starts with: (torch, the scene's torch device, the stream — torch's current one
+        if none was given —, the context that makes it torch's current stream while the call allocates, or a null
+        context for a raw hipStream_t, and the raw handle for the descriptor)."""
+        import torch                              # here: `import rtamd` needs no torch
+
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+        return torch, dev, stream, ctx, _raw_stream(stream)
 
     # ---- lifecycle ---------------------------------------------------------------------
     def build_acceleration_structure(self, seed: int = 0, mode: str = "compat"):
@@ -157,13 +192,12 @@ class Renderer:
             torch = sys.modules.get("torch")       # never imported here: `import rtamd` needs no torch
             if torch is not None and torch.cuda.is_available():
                 stream = torch.cuda.current_stream(self.device)
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
         u = abi.TriangleUpdate()
         u.first, u.count = first, n
         u.vertices_device = vptr or None
         u.normals_device = nptr or None
         u.flags = (0 if sync else abi.RT_TRI_UPDATE_NO_SYNC) | (abi.RT_TRI_UPDATE_BOUNDS if bounds else 0)
-        u.stream = raw or None
+        u.stream = _raw_stream(stream)
         abi.check(self.lib, self.lib.rt_scene_update_triangles_device(self.h, C.byref(u)))
         return self
 
@@ -305,15 +339,10 @@ class Renderer:
         Closest mode returns (t float32 [N] with +inf on a miss, hits uint8 [N, 48] rt_hit records — see
         hits_to_numpy — or None without want_hits); any_hit returns occluded bool [N].  With sync=False the call
         returns after the enqueue and the tensors are valid in stream order."""
-        import torch                              # here: `import rtamd` needs no torch
-
-        dev = torch.device("cuda", self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        # uploads and outputs are made on the query's stream, so they are ordered with the launch and torch's
+        # uploads and outputs are made on the query's stream (ctx), so they are ordered with the launch and torch's
         # allocator orders their reuse with it.  A raw hipStream_t gives torch nothing to order with: a numpy input's
         # upload is then waited for, and the call waits for the query before the temporary is released.
-        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+        torch, dev, stream, ctx, raw = self._torch_call(stream)
         uploaded = []
 
         def device_f32(x, shape, name):
@@ -342,14 +371,13 @@ class Renderer:
         if uploaded and not isinstance(stream, torch.cuda.Stream):
             torch.cuda.current_stream(dev).synchronize()
             sync = True
-        raw = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
         q = abi.RayQuery()
         q.rays_device = rays.data_ptr() if n else None
         q.tmax_device = tmax.data_ptr() if (tmax is not None and n) else None
         q.ray_count = n
         q.flags = (abi.RT_QUERY_EXACT if exact else 0) | (abi.RT_QUERY_ANY_HIT if any_hit else 0) | \
                   (0 if sync else abi.RT_QUERY_NO_SYNC)
-        q.stream = raw or None
+        q.stream = raw
         with ctx:
             if any_hit:
                 occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
@@ -375,19 +403,14 @@ class Renderer:
         material's albedo, the background on a miss).  stream: a torch.cuda.Stream or a raw hipStream_t (None =
         torch's current stream); with sync=False the call returns after the enqueue and the tensors are valid in
         stream order."""
-        import torch                              # here: `import rtamd` needs no torch
-
-        dev = torch.device("cuda", self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
+        torch, dev, stream, ctx, raw = self._torch_call(stream)
         x0, y0, w, h = (0, 0, self.width, self.height) if rect is None else (int(v) for v in rect)
         q = abi.CameraQuery()
         q.x0, q.y0, q.width, q.height = x0, y0, w, h
         q.frame_seed = frame_seed
         q.flags = (abi.RT_CAMERA_QUERY_EXACT if exact else 0) | (0 if sync else abi.RT_CAMERA_QUERY_NO_SYNC) | \
                   (abi.RT_CAMERA_QUERY_FIRST_SAMPLE if first_sample else 0)
-        q.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        q.stream = raw
         out = {}
         with ctx:                                 # outputs made on the query's stream, as query_rays
             for want, key, field, tail, dtype in ((want_rays, "rays", "rays_device", (6,), torch.float32),
@@ -412,32 +435,14 @@ class Renderer:
         which may be rgb itself (None: a new one).  Returns {"rgb": out} and, with want_rgba, "rgba" uint8 [h, w, 4].
         stream: a torch.cuda.Stream or a raw hipStream_t (None = torch's current stream); the scratch and the outputs
         are allocated on it, and with sync=False the call returns after the enqueue."""
-        import torch                              # here: `import rtamd` needs no torch
+        torch, dev, stream, ctx, raw = self._torch_call(stream)
 
-        dev = torch.device("cuda", self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
-
-        def checked(x, tail, dtype, name):
-            if not isinstance(x, torch.Tensor):
-                raise ValueError(f"{name}: a torch tensor")
-            if x.dtype != dtype:
-                raise ValueError(f"{name}: {dtype}, not {x.dtype}")
-            if x.device != dev:
-                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
-            if x.dim() != 3 or x.shape[2] != tail:
-                raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
-            if not x.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-            return x
-
-        rgb = checked(rgb, 3, torch.float32, "rgb")
+        rgb = checked(rgb, 3, torch.float32, "rgb", dev)
         h, w = int(rgb.shape[0]), int(rgb.shape[1])
         for x, tail, dtype, name in ((hits, C.sizeof(abi.Hit), torch.uint8, "hits"), (albedo, 3, torch.float32, "albedo"),
                                      (out, 3, torch.float32, "out")):
             if x is not None or name == "hits":
-                if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
+                if tuple(checked(x, tail, dtype, name, dev).shape[:2]) != (h, w):
                     raise ValueError(f"{name}: {tuple(x.shape[:2])}, rgb is {(h, w)}")
         if not isinstance(stream, torch.cuda.Stream):
             sync = True      # a raw hipStream_t gives torch nothing to order the scratch's release with (as query_rays)
@@ -446,7 +451,7 @@ class Renderer:
         d.flags = 0 if sync else abi.RT_DENOISE_NO_SYNC
         d.sigma_color, d.sigma_normal, d.sigma_plane = float(sigma_color), float(sigma_normal), float(sigma_plane)
         d.scratch_bytes = self.lib.rt_denoise_scratch_bytes(w, h)
-        d.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        d.stream = raw
         with ctx:                                 # made on the call's stream, as query_camera's outputs
             if out is None:
                 out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
@@ -481,27 +486,9 @@ class Renderer:
         moments=True is rt_accumulate_moments (include/rt.h, "Variance-guided denoising"): the same history and rgb, and
         the dict also holds "moments", float32 [h, w, 2], the first two moments of the luminance of rgb / albedo (albedo:
         float32 [h, w, 3], optional, the one denoise_guided will be given); prev must then be a dict of such a call."""
-        import torch                              # here: `import rtamd` needs no torch
+        torch, dev, stream, ctx, raw = self._torch_call(stream)
 
-        dev = torch.device("cuda", self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
-
-        def checked(x, tail, dtype, name):
-            if not isinstance(x, torch.Tensor):
-                raise ValueError(f"{name}: a torch tensor")
-            if x.dtype != dtype:
-                raise ValueError(f"{name}: {dtype}, not {x.dtype}")
-            if x.device != dev:
-                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
-            if x.dim() != 3 or x.shape[2] != tail:
-                raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
-            if not x.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-            return x
-
-        rgb = checked(rgb, 3, torch.float32, "rgb")
+        rgb = checked(rgb, 3, torch.float32, "rgb", dev)
         h, w = int(rgb.shape[0]), int(rgb.shape[1])
         nhit = C.sizeof(abi.Hit)
         named = [(hits, nhit, torch.uint8, "hits")]
@@ -519,7 +506,7 @@ class Renderer:
             if albedo is not None:
                 named.append((albedo, 3, torch.float32, "albedo"))
         for x, tail, dtype, name in named:
-            if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
+            if tuple(checked(x, tail, dtype, name, dev).shape[:2]) != (h, w):
                 raise ValueError(f"{name}: {tuple(x.shape[:2])}, rgb is {(h, w)}")
         if prev_view is not None and not isinstance(prev_view, abi.Reprojection):
             raise ValueError("prev_view: an abi.Reprojection (rtamd.reprojection)")
@@ -529,7 +516,7 @@ class Renderer:
         d.width, d.height = w, h
         d.flags = 0 if sync else abi.RT_ACCUMULATE_NO_SYNC
         d.max_history, d.normal_cos, d.plane_tolerance = float(max_history), float(normal_cos), float(plane_tolerance)
-        d.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        d.stream = raw
         with ctx:                                 # made on the call's stream, as query_camera's outputs
             history = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
             if out_rgb is None:
@@ -565,35 +552,17 @@ class Renderer:
         out: the float32 [h, w, 3] tensor to write (None: a new one).  Returns {"rgb": out} and, with want_rgba, "rgba"
         uint8 [h, w, 4]; with want_variance, "variance" float32 [h, w], the variance of the accumulated luminance the
         first pass starts from.  stream and sync as denoise."""
-        import torch                              # here: `import rtamd` needs no torch
-
-        dev = torch.device("cuda", self.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        ctx = torch.cuda.stream(stream) if isinstance(stream, torch.cuda.Stream) else _null_context()
-
-        def checked(x, tail, dtype, name):
-            if not isinstance(x, torch.Tensor):
-                raise ValueError(f"{name}: a torch tensor")
-            if x.dtype != dtype:
-                raise ValueError(f"{name}: {dtype}, not {x.dtype}")
-            if x.device != dev:
-                raise ValueError(f"{name}: on {x.device}, the scene is on {dev}")
-            if x.dim() != 3 or x.shape[2] != tail:
-                raise ValueError(f"{name}: shape [h, w, {tail}], not {tuple(x.shape)}")
-            if not x.is_contiguous():
-                raise ValueError(f"{name}: not contiguous")
-            return x
+        torch, dev, stream, ctx, raw = self._torch_call(stream)
 
         if not isinstance(acc, dict) or "moments" not in acc:
             raise ValueError("acc: the dict accumulate(..., moments=True) returned")
-        history = checked(acc["history"], 4, torch.float32, "history")
+        history = checked(acc["history"], 4, torch.float32, "history", dev)
         h, w = int(history.shape[0]), int(history.shape[1])
         for x, tail, dtype, name in ((acc["moments"], 2, torch.float32, "moments"),
                                      (acc["hits"], C.sizeof(abi.Hit), torch.uint8, "hits"),
                                      (albedo, 3, torch.float32, "albedo"), (out, 3, torch.float32, "out")):
             if x is not None or name in ("moments", "hits"):
-                if tuple(checked(x, tail, dtype, name).shape[:2]) != (h, w):
+                if tuple(checked(x, tail, dtype, name, dev).shape[:2]) != (h, w):
                     raise ValueError(f"{name}: {tuple(x.shape[:2])}, the history is {(h, w)}")
         if not isinstance(stream, torch.cuda.Stream):
             sync = True      # a raw hipStream_t gives torch nothing to order the scratch's release with (as denoise)
@@ -602,7 +571,7 @@ class Renderer:
         d.flags = 0 if sync else abi.RT_DENOISE_NO_SYNC
         d.sigma_luminance, d.sigma_normal, d.sigma_plane = float(sigma_luminance), float(sigma_normal), float(sigma_plane)
         d.scratch_bytes = self.lib.rt_denoise_guided_scratch_bytes(w, h)
-        d.stream = (stream.cuda_stream if hasattr(stream, "cuda_stream") else stream) or None
+        d.stream = raw
         with ctx:                                 # made on the call's stream, as query_camera's outputs
             if out is None:
                 out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
