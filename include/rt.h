@@ -38,7 +38,9 @@ extern "C" {
  *     rt_denoise / rt_denoise_scratch_bytes / rt_denoise_desc arrived within 5 the same way;
  *     rt_accumulate / rt_accumulate_desc / rt_camera_reprojection / rt_reprojection arrived within 5 the same way;
  *     rt_accumulate_moments / rt_moments_desc / rt_denoise_guided / rt_denoise_guided_scratch_bytes /
- *     rt_denoise_guided_desc arrived within 5 the same way) */
+ *     rt_denoise_guided_desc arrived within 5 the same way;
+ *     rt_instance_motion_records / rt_instance_motion / rt_accumulate_motion / rt_motion_desc arrived within 5 the same
+ *     way) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -546,9 +548,11 @@ rt_status rt_denoise(int device, const rt_denoise_desc *desc);
  *              history[k] = out, rgb32[k] = out.rgb.
  *            In float32 without FMA contraction, IEEE division, no transcendental function: the float32 restatement
  *            in tests/accumulate_ref.py gives the kernel's bits.
- * Not done : instance motion is not compensated (a moved instance is caught only by the plane test, so its pixels
- *            restart); no 3 x 3 fallback search around a failed reprojection; sky is not reused.  (Luminance moments
- *            and the variance-guided filter: rt_accumulate_moments and rt_denoise_guided below.)
+ * Not done : no 3 x 3 fallback search around a failed reprojection; sky is not reused.  rt_accumulate itself does not
+ *            compensate instance motion (a moved instance is caught by the plane test, so its pixels restart):
+ *            rt_accumulate_motion below does.  Shadows and reflections of a moving instance on static pixels are not
+ *            compensated by either: the surface has not moved, so its history is kept while its shading changes.
+ *            (Luminance moments and the variance-guided filter: rt_accumulate_moments and rt_denoise_guided below.)
  * Outputs  : history_device (required): float4 per pixel, next frame's prev_history_device.  rgb32_device (optional):
  *            3 floats per pixel, out.rgb; it may be color_device itself (a thread reads only its own pixel's colour).
  *            Otherwise no output may overlap an input or the other output: the byte ranges are compared on the host.
@@ -652,9 +656,11 @@ rt_status rt_accumulate(int device, const rt_accumulate_desc *desc);
  *            the box |dx|, |dy| <= 2 (2^iterations - 1) around it, across the hit / sky boundary too (0 * NaN), and
  *            to no other pixel; v_0 reads no colour and is unaffected.  Non-finite moments are not detected either
  *            and their effect is unspecified (an infinite variance gives k(p) = 0 and a finite result).
- * Not done : the filtered colour of the first pass is not fed back as history (SVGF does); moving instances are not
- *            compensated (as rt_accumulate); the colour accumulates modulated while the moments are demodulated, so
- *            where the albedo changes under a kept pixel the two disagree for up to max_history frames. */
+ * Not done : the filtered colour of the first pass is not fed back as history (SVGF does); moving instances are
+ *            compensated by rt_accumulate_motion ("Moving instances" below), not by rt_accumulate_moments, and the
+ *            shadows and reflections a moving instance casts on static pixels by neither; the colour accumulates
+ *            modulated while the moments are demodulated, so where the albedo changes under a kept pixel the two
+ *            disagree for up to max_history frames. */
 typedef struct rt_moments_desc {
     const float *albedo_device;        /* optional, 3 floats per pixel: the albedo the guided filter will be given */
     const float *prev_moments_device;  /* last call's moments_device; NULL exactly when desc->prev_history_device is NULL */
@@ -685,6 +691,84 @@ typedef struct rt_denoise_guided_desc {
 
 uint64_t  rt_denoise_guided_scratch_bytes(uint32_t width, uint32_t height);
 rt_status rt_denoise_guided(int device, const rt_denoise_guided_desc *desc);
+
+/* Moving instances: rt_accumulate and rt_accumulate_moments reproject a pixel's hit point as if the surface had stood
+ * still, so on an instance that moved the point lands on a previous record of where the surface was, the plane test
+ * rejects it and the pixel restarts, every frame.  rt_accumulate_motion first carries the point and the normal back to
+ * where their instance was in the previous frame, and runs the reprojection and the instance, normal and plane tests
+ * there.  The accumulation stays scene-less: rt_instance_motion_records derives one record per instance, on the host
+ * and without a scene or a GPU (as rt_camera_reprojection), from the two rt_xform arrays the caller holds anyway, the
+ * caller uploads the records, and the kernel reads the one rt_hit.instance names.
+ *
+ * rt_instance_motion_records: for each instance i of `count`:
+ *            prev[i] and cur[i] bytewise equal: flags = RT_MOTION_STATIC, point = the identity rows, normal = the
+ *            identity.
+ *            Otherwise Fp and Fc are the float forward matrices of prev[i] and cur[i] exactly as rt_scene_update
+ *            derives them (one shared function: (shift * ((Rx * Ry) * Rz)) * scale from the host's cos and sin of the
+ *            degrees); Lp, tp, Lc, tc their 3 x 3 linear parts and translations, widened to double.  In double, with
+ *            every product and sum rounded on its own:
+ *              C(L)[i][j] = L[i+1][j+1] L[i+2][j+2] - L[i+1][j+2] L[i+2][j+1] (indices modulo 3: the cofactors);
+ *              det(L) = (L[0][0] C[0][0] + L[0][1] C[0][1]) + L[0][2] C[0][2];   L^-1[i][j] = C[j][i] / det;
+ *              A = Lp Lc^-1 and M = Lc Lp^-1, each element (X[i][0] Y[0][j] + X[i][1] Y[1][j]) + X[i][2] Y[2][j];
+ *              b[i] = tp[i] - ((A[i][0] tc[0] + A[i][1] tc[1]) + A[i][2] tc[2]);   Nn = M^T.
+ *            point = the rows (A | b) and normal = Nn, each value rounded to float; flags = RT_MOTION_MOVED.
+ *            flags = RT_MOTION_NO_HISTORY with point and normal all zero when either determinant is 0 or not finite,
+ *            when any resulting float is not finite, or when either forward matrix is one the library does not invert
+ *            (a pivot of the reference's elimination below 1e-6, Matrix.cu:5-68: such an instance is traced with its
+ *            forward matrix in the inverse's place, and its hit points say nothing about the surface).  A scale of 0
+ *            is legal input.
+ *            RT_ERR_INVALID_ARGUMENT for a NULL pointer with count > 0; count == 0 is RT_OK.
+ * rt_accumulate_motion does all of rt_accumulate(device, desc) when `moments` is NULL and all of
+ * rt_accumulate_moments(device, desc, moments) otherwise: their argument checks, ordering, NO_SYNC flag and outputs.
+ * One kernel, instantiated with and without the motion: per pixel, with inst = rec.instance, x and n as stored, still in
+ * float32 without FMA contraction:
+ *              inst >= instance_count: handled as static; nothing is read from the records.
+ *              f = motion[inst].flags.
+ *              f == RT_MOTION_STATIC: xp = x, np = n, no arithmetic: the pixel gets rt_accumulate's bits.
+ *              f == RT_MOTION_MOVED: with P = point (3 rows of 4) and Nn = normal (3 rows of 3), per component c:
+ *                xp.c = ((P[c][0] x.x + P[c][1] x.y) + P[c][2] x.z) + P[c][3];
+ *                u.c = (Nn[c][0] n.x + Nn[c][1] n.y) + Nn[c][2] n.z;   l2 = (u.x u.x + u.y u.y) + u.z u.z;
+ *                reset unless l2 > 0 (a NaN fails);  s = sqrtf(l2), correctly rounded;  np.c = u.c / s.
+ *              any other f (RT_MOTION_NO_HISTORY included): reset.
+ *              Everything after that is rt_accumulate's text with xp for x and np for n: v = xp - centre, the taps,
+ *              (np . m.normal) >= normal_cos, e = m.point - xp, fabsf(np . e) <= plane_tolerance * rec.t.  The
+ *              tolerance keeps the current frame's t, m.instance == inst stays, the blend and the moments are unchanged.
+ *            tests/motion_ref.py restates it in float32 and gives the kernel's bits.
+ *            The records are not validated on the device.  Non-finite matrix elements behave like non-finite points:
+ *            the window test on fx, fy or l2 > 0 resets the pixel.
+ * Errors   : rt_accumulate's (and rt_accumulate_moments' when `moments` is given), and, before anything is enqueued
+ *            and without a GPU, RT_ERR_INVALID_ARGUMENT for a NULL motion, reserved != 0, instance_count above
+ *            0xFFFFFFFE, exactly one of motion_device and instance_count being zero, a motion_device that is not
+ *            16-byte aligned or whose instance_count records overlap any output, and instance_count > 0 together with a
+ *            prev_history_device and a NULL prev_view (a moved point needs a camera to land in: a caller whose camera
+ *            stands still passes the current camera's rows); then for a motion_device the device cannot access.
+ *            width * height == 0 returns RT_OK and touches no device.
+ * Not done : motion of the geometry inside an instance (rt_scene_update_triangles*) has no per-instance map; shadows
+ *            and reflections of a moving instance on static pixels are not compensated. */
+typedef struct rt_instance_motion {
+    float point[12];     /* rows of the 3 x 4 map: previous-frame world point = A x + b, x a current-frame world point */
+    float normal[9];     /* rows of the 3 x 3 map of normals, (A^-1)^T; its result is normalised by the kernel */
+    uint32_t flags;      /* rt_instance_motion_flags */
+    uint32_t reserved[2];/* 0 */
+} rt_instance_motion;    /* 96 bytes */
+
+typedef enum rt_instance_motion_flags {
+    RT_MOTION_STATIC = 0,      /* the instance did not move: the pixel is handled exactly as rt_accumulate handles it */
+    RT_MOTION_MOVED = 1,       /* apply point[] and normal[] */
+    RT_MOTION_NO_HISTORY = 2   /* every pixel of the instance resets (new, teleported, singular transform) */
+} rt_instance_motion_flags;
+
+rt_status rt_instance_motion_records(const rt_xform *prev, const rt_xform *cur, size_t count, rt_instance_motion *out);
+
+typedef struct rt_motion_desc {
+    const rt_instance_motion *motion_device;  /* instance_count records, 16-byte aligned, indexed by rt_hit.instance */
+    uint64_t instance_count;                  /* <= 0xFFFFFFFE; 0 with motion_device NULL = no instance moves */
+    uint64_t reserved;                        /* 0 */
+} rt_motion_desc;                             /* 24 bytes on LP64 */
+
+rt_status rt_accumulate_motion(int device, const rt_accumulate_desc *desc,
+                               const rt_moments_desc *moments /* NULL: as rt_accumulate */,
+                               const rt_motion_desc *motion);
 
 /* The box decisions of the trace kernels on caller data, for parity tests (no scene needed): box i =
  * {xmin, xmax, ymin, ymax, zmin, zmax} (6 floats), ray i = origin xyz, direction xyz, range [0.001, tmax[i]].

@@ -18,6 +18,11 @@
 //   the first two moments of the demodulated luminance (include/rt.h, "Variance-guided denoising"): 12 B of albedo and
 //   up to four float2 read, one float2 written.  MOMENTS = false compiles to what it was before the template
 //   (profiles/guided/kernel_resources.txt: 33 VGPRs, as profiles/accumulate/kernel_resources.txt).
+//   rt_accumulate_motion is the same function with MOTION = true (include/rt.h, "Moving instances"): before the
+//   reprojection the pixel's point and normal are carried to where their instance stood in the previous frame by the
+//   instance's rt_instance_motion record, 96 B that the lanes of a wave mostly share (a near-uniform gather, read with
+//   plain vector loads: the flags first, the five float4 and one float of the matrices only when the instance moved).
+//   The four MOTION = false instantiations are the kernels they were, byte for byte (profiles/motion/README.md).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -35,7 +40,7 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
     return (ax * bx + ay * by) + az * bz;
 }
 
-template <bool MOMENTS>
+template <bool MOMENTS, bool MOTION>
 __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, int j) {
     const size_t k = (size_t)j * g.w + (size_t)i;
     const float cr = g.color[3 * k + 0], cg = g.color[3 * k + 1], cb = g.color[3 * k + 2];
@@ -56,13 +61,35 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, 
     const rt_hit *rec = g.hits + k;
     const uint32_t inst = rec->instance;
     if (g.prev_history && inst != ACC_MISS) {
-        const float px = rec->point.x, py = rec->point.y, pz = rec->point.z;
-        const float nx = rec->normal.x, ny = rec->normal.y, nz = rec->normal.z;
+        float px = rec->point.x, py = rec->point.y, pz = rec->point.z;
+        float nx = rec->normal.x, ny = rec->normal.y, nz = rec->normal.z;
         const float tol = g.plane_tolerance * rec->t;
         int ix = i, iy = j;
         float wx = 0.0f, wy = 0.0f;
         bool ok = true;
-        if (g.has_view) {
+        if (MOTION && inst < g.motion_count) {                        // past the records: static, and nothing is read
+            const rt_instance_motion *mr = g.motion + inst;
+            const uint32_t f = mr->flags;
+            if (f == RT_MOTION_MOVED) {                               // the point and the normal where the instance was
+                const float4 *rows = reinterpret_cast<const float4 *>(mr);          // 16-byte aligned by contract
+                const float4 p0 = rows[0], p1 = rows[1], p2 = rows[2], n0 = rows[3], n1 = rows[4];
+                const float n22 = mr->normal[8];
+                const float qx = ((p0.x * px + p0.y * py) + p0.z * pz) + p0.w;
+                const float qy = ((p1.x * px + p1.y * py) + p1.z * pz) + p1.w;
+                const float qz = ((p2.x * px + p2.y * py) + p2.z * pz) + p2.w;
+                const float ux = dot3(n0.x, n0.y, n0.z, nx, ny, nz);
+                const float uy = dot3(n0.w, n1.x, n1.y, nx, ny, nz);
+                const float uz = dot3(n1.z, n1.w, n22, nx, ny, nz);
+                const float l2 = dot3(ux, uy, uz, ux, uy, uz);
+                ok = l2 > 0.0f;                                       // a NaN fails
+                const float s = sqrtf(l2);
+                px = qx; py = qy; pz = qz;
+                nx = ux / s; ny = uy / s; nz = uz / s;
+            } else if (f != RT_MOTION_STATIC) {
+                ok = false;                                           // RT_MOTION_NO_HISTORY and every unknown value
+            }
+        }
+        if ((!MOTION || ok) && g.has_view) {
             const rt_reprojection &m = g.view;
             const float vx = px - m.centre[0], vy = py - m.centre[1], vz = pz - m.centre[2];
             const float r0 = dot3(m.rx[0], m.rx[1], m.rx[2], vx, vy, vz);
@@ -125,21 +152,21 @@ __device__ __forceinline__ void accumulate_pixel(const AccumulateGPU &g, int i, 
 }
 
 // blockDim (64, 4): a wave is 64 consecutive pixels of one row
-template <bool MOMENTS>
+template <bool MOMENTS, bool MOTION>
 __global__ __launch_bounds__(256) void accumulate_rows_kernel(AccumulateGPU g) {
     const int x = (int)(blockIdx.x * 64u + threadIdx.x), y = (int)(blockIdx.y * 4u + threadIdx.y);
     if (x >= (int)g.w || y >= (int)g.h) return;
-    accumulate_pixel<MOMENTS>(g, x, y);
+    accumulate_pixel<MOMENTS, MOTION>(g, x, y);
 }
 
 // blockDim 256, a 16 x 16 tile: wave w is the 8 x 8 block (w & 1, w >> 1) of it, lane l its pixel (l & 7, l >> 3)
-template <bool MOMENTS>
+template <bool MOMENTS, bool MOTION>
 __global__ __launch_bounds__(256) void accumulate_blocks_kernel(AccumulateGPU g) {
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const int x = (int)(blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u));
     const int y = (int)(blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3));
     if (x >= (int)g.w || y >= (int)g.h) return;
-    accumulate_pixel<MOMENTS>(g, x, y);
+    accumulate_pixel<MOMENTS, MOTION>(g, x, y);
 }
 
 // The mapping: 'r' rows, 'b' blocks.  scripts/accumulate_bench.py measures them side by side, alternating in one
@@ -151,17 +178,26 @@ char pixel_mapping() {
     return e && (e[0] == 'r' || e[0] == 'b') && e[1] == 0 ? e[0] : ACC_FORM;
 }
 
-}  // namespace
-
-// g.moments set: rt_accumulate_moments' instantiation
-hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream) {
-    const bool rows = pixel_mapping() == 'r';
+template <bool MOMENTS, bool MOTION>
+void launch_mapping(const AccumulateGPU &g, bool rows, hipStream_t stream) {
     const dim3 grid = rows ? dim3((g.w + 63u) / 64u, (g.h + 3u) / 4u) : dim3((g.w + 15u) / 16u, (g.h + 15u) / 16u);
     const dim3 block = rows ? dim3(64, 4) : dim3(256);
-    if (g.moments)
-        hipLaunchKernelGGL(rows ? accumulate_rows_kernel<true> : accumulate_blocks_kernel<true>, grid, block, 0, stream, g);
-    else
-        hipLaunchKernelGGL(rows ? accumulate_rows_kernel<false> : accumulate_blocks_kernel<false>, grid, block, 0, stream, g);
+    hipLaunchKernelGGL((rows ? accumulate_rows_kernel<MOMENTS, MOTION> : accumulate_blocks_kernel<MOMENTS, MOTION>), grid, block,
+                       0, stream, g);
+}
+
+}  // namespace
+
+// g.moments set: rt_accumulate_moments' instantiation; g.motion set: rt_accumulate_motion's
+hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream) {
+    const bool rows = pixel_mapping() == 'r';
+    if (g.motion) {
+        if (g.moments) launch_mapping<true, true>(g, rows, stream);
+        else launch_mapping<false, true>(g, rows, stream);
+    } else {
+        if (g.moments) launch_mapping<true, false>(g, rows, stream);
+        else launch_mapping<false, false>(g, rows, stream);
+    }
     return hipGetLastError();
 }
 

@@ -1,7 +1,9 @@
-// filters.cpp — the image filters: rt_denoise (denoise.hip), rt_accumulate / _moments (accumulate.hip) and
+// filters.cpp — the image filters: rt_denoise (denoise.hip), rt_accumulate / _moments / _motion (accumulate.hip) and
 // rt_denoise_guided (guided.hip).  They take no scene: `int device` and a descriptor of caller buffers.  Every call has
 // the same shape: the argument checks, which need no device and come in the order the ABI tests pin; the device and the
-// buffers' accessibility from it; the launcher; the tail.
+// buffers' accessibility from it; the launcher; the tail.  rt_instance_motion_records, the host-only helper that feeds
+// rt_accumulate_motion, is here too (its arithmetic: instance_motion.hpp).
+#include "instance_motion.hpp"
 #include "launch.hpp"
 #include "scene.hpp"
 
@@ -43,11 +45,13 @@ rt_status finish(hipStream_t st, bool no_sync) {
     return RT_OK;
 }
 
-// rt_accumulate (m == nullptr, with_moments false) and rt_accumulate_moments: one set of checks, one launcher
-rt_status accumulate_call(int device, const rt_accumulate_desc *d, const rt_moments_desc *m, bool with_moments) {
-    const std::string name = with_moments ? "rt_accumulate_moments" : "rt_accumulate";
+// rt_accumulate (m == nullptr, with_moments false), rt_accumulate_moments and rt_accumulate_motion (with_motion; m is
+// then optional): one set of checks, one launcher
+rt_status accumulate_call(int device, const rt_accumulate_desc *d, const rt_moments_desc *m, bool with_moments,
+                          const rt_motion_desc *mo = nullptr, bool with_motion = false) {
+    const std::string name = with_motion ? "rt_accumulate_motion" : with_moments ? "rt_accumulate_moments" : "rt_accumulate";
     // the argument checks need no device
-    if (!d || (with_moments && !m)) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (!d || (with_moments && !m) || (with_motion && !mo)) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
     if (d->reserved != 0 || d->reserved1 != 0 || (d->flags & ~(uint32_t)RT_ACCUMULATE_NO_SYNC) || (m && m->reserved != 0))
         return fail(RT_ERR_INVALID_ARGUMENT, name + ": reserved bits set");
     if (d->width > 16384 || d->height > 16384) return fail(RT_ERR_INVALID_ARGUMENT, name + ": width and height are at most 16384");
@@ -80,6 +84,18 @@ rt_status accumulate_call(int device, const rt_accumulate_desc *d, const rt_mome
                  overlap(moments, history) || overlap(moments, rgb) || overlap(moments, color);
     for (const Range &r : read) clash = clash || overlap(history, r) || overlap(rgb, r) || overlap(moments, r);
     if (clash) return fail(RT_ERR_INVALID_ARGUMENT, name + ": an output overlaps another buffer");
+    if (mo) {
+        if (mo->reserved != 0) return fail(RT_ERR_INVALID_ARGUMENT, name + ": reserved bits set");
+        if (mo->instance_count > 0xFFFFFFFEull) return fail(RT_ERR_INVALID_ARGUMENT, name + ": instance_count is at most 0xFFFFFFFE");
+        if (!mo->motion_device != !mo->instance_count)
+            return fail(RT_ERR_INVALID_ARGUMENT, name + ": motion_device and instance_count go together");
+        if ((uintptr_t)mo->motion_device & 15u) return fail(RT_ERR_INVALID_ARGUMENT, name + ": motion_device must be 16-byte aligned");
+        const Range records{mo->motion_device, sizeof(rt_instance_motion) * mo->instance_count};
+        if (overlap(history, records) || overlap(rgb, records) || overlap(moments, records))
+            return fail(RT_ERR_INVALID_ARGUMENT, name + ": an output overlaps the motion records");
+        if (mo->instance_count && d->prev_history_device && !d->prev_view)
+            return fail(RT_ERR_INVALID_ARGUMENT, name + ": motion records need prev_view (a still camera passes its own rows)");
+    }
     if (n == 0) return RT_OK;
     DeviceRestore restore;
     RT_TRY(select_device(device));
@@ -87,6 +103,7 @@ rt_status accumulate_call(int device, const rt_accumulate_desc *d, const rt_mome
                            d->rgb32_device, m ? m->albedo_device : nullptr, m ? m->prev_moments_device : nullptr,
                            m ? m->moments_device : nullptr},
                           device, name + ": a buffer is not accessible from the device"));
+    if (mo) RT_TRY(all_accessible({mo->motion_device}, device, name + ": motion_device is not accessible from the device"));
 
     AccumulateGPU g{};
     g.color = d->color_device; g.hits = d->hits_device; g.prev_hits = d->prev_hits_device;
@@ -101,6 +118,7 @@ rt_status accumulate_call(int device, const rt_accumulate_desc *d, const rt_mome
         g.prev_moments = reinterpret_cast<const float2 *>(m->prev_moments_device);
         g.moments = reinterpret_cast<float2 *>(m->moments_device);
     }
+    if (mo) { g.motion = mo->motion_device; g.motion_count = (uint32_t)mo->instance_count; }   // none: MOTION = false kernels
     hipStream_t st = static_cast<hipStream_t>(d->stream);
     HIP_TRY(launch_accumulate(g, st));
     return finish(st, (d->flags & RT_ACCUMULATE_NO_SYNC) != 0);
@@ -149,6 +167,17 @@ rt_status rt_accumulate(int device, const rt_accumulate_desc *d) { return accumu
 
 rt_status rt_accumulate_moments(int device, const rt_accumulate_desc *d, const rt_moments_desc *m) {
     return accumulate_call(device, d, m, true);
+}
+
+rt_status rt_accumulate_motion(int device, const rt_accumulate_desc *d, const rt_moments_desc *m, const rt_motion_desc *mo) {
+    return accumulate_call(device, d, m, m != nullptr, mo, true);
+}
+
+rt_status rt_instance_motion_records(const rt_xform *prev, const rt_xform *cur, size_t count, rt_instance_motion *out) {
+    if (count == 0) return RT_OK;
+    if (!prev || !cur || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    for (size_t i = 0; i < count; i++) out[i] = motion_record(prev[i], cur[i]);
+    return RT_OK;
 }
 
 uint64_t rt_denoise_guided_scratch_bytes(uint32_t width, uint32_t height) { return scratch_bytes(width, height); }

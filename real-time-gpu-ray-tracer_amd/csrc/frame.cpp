@@ -8,16 +8,12 @@ namespace {
 // Instance::updateTransformArguments (src/AS/Instance.cu:4-17)
 hm::V3 cos3(const rt_xform &x) {
     hm::V3 c, s;
-    hm::rotate_cos_sin(x.rotate_deg.x, c.x, s.x);
-    hm::rotate_cos_sin(x.rotate_deg.y, c.y, s.y);
-    hm::rotate_cos_sin(x.rotate_deg.z, c.z, s.z);
+    hm::xform_cos_sin(x, c, s);
     return c;
 }
 hm::V3 sin3(const rt_xform &x) {
     hm::V3 c, s;
-    hm::rotate_cos_sin(x.rotate_deg.x, c.x, s.x);
-    hm::rotate_cos_sin(x.rotate_deg.y, c.y, s.y);
-    hm::rotate_cos_sin(x.rotate_deg.z, c.z, s.z);
+    hm::xform_cos_sin(x, c, s);
     return s;
 }
 
@@ -32,7 +28,7 @@ namespace rtamd {
 
 void instance_update(InstState &in, const rt_xform &x) {
     in.x = x;
-    in.fwd = hm::instance_matrix(hm::of(x.shift), cos3(x), sin3(x), hm::of(x.scale));
+    in.fwd = hm::instance_forward(x);             // shared with rt_instance_motion_records (instance_motion.hpp)
     in.inv = hm::inverse(in.fwd);
     in.nrm = hm::transpose(in.inv);
     in.tbox = hm::transform_box(in.box, in.fwd);

@@ -171,6 +171,18 @@ HM_HD inline Mat instance_matrix(V3 shift, V3 c, V3 s, V3 scale) {
     return shift_matrix(shift) * ((rotate_matrix_cs(c.x, s.x, 0) * rotate_matrix_cs(c.y, s.y, 1)) * rotate_matrix_cs(c.z, s.z, 2)) *
            scale_matrix(scale);
 }
+// ... and from an rt_xform on the host: the forward matrix of rt_scene_update's instances (frame.cpp) and of
+// rt_instance_motion_records (instance_motion.hpp), one cos / sin evaluation per angle
+inline void xform_cos_sin(const rt_xform &x, V3 &c, V3 &s) {
+    rotate_cos_sin(x.rotate_deg.x, c.x, s.x);
+    rotate_cos_sin(x.rotate_deg.y, c.y, s.y);
+    rotate_cos_sin(x.rotate_deg.z, c.z, s.z);
+}
+inline Mat instance_forward(const rt_xform &x) {
+    V3 c, s;
+    xform_cos_sin(x, c, s);
+    return instance_matrix(of(x.shift), c, s, of(x.scale));
+}
 HM_HD inline V3 apply_point(const Mat &m, V3 p) {           // (M * toMatrix(Point3)).toPoint()
     V3 r;
     for (int i = 1; i <= 3; i++) {

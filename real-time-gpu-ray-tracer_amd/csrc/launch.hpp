@@ -91,6 +91,9 @@ struct AccumulateGPU {
     const float *albedo;
     const float2 *prev_moments;
     float2 *moments;
+    // rt_accumulate_motion only (motion set): motion_count records indexed by rt_hit.instance; none past them is read
+    const rt_instance_motion *motion;
+    uint32_t motion_count;
 };
 // one launch, one thread per pixel
 hipError_t launch_accumulate(const AccumulateGPU &g, hipStream_t stream);

@@ -4,6 +4,6 @@ The product is librtamd.so (C ABI in include/rt.h; hand-written HIP kernels for 
 This package is the Python host mirror used by tests and benchmarks.
 """
 from . import abi, scenes  # noqa: F401
-from .renderer import Renderer, reprojection  # noqa: F401
+from .renderer import Renderer, instance_motion, reprojection  # noqa: F401
 
-__all__ = ["abi", "scenes", "Renderer", "reprojection"]
+__all__ = ["abi", "scenes", "Renderer", "reprojection", "instance_motion"]

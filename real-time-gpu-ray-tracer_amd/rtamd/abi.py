@@ -178,6 +178,20 @@ class MomentsDesc(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class InstanceMotion(C.Structure):
+    """rt_instance_motion: the record that carries a point and a normal of one instance back to the previous frame
+    (rt_instance_motion_records)."""
+    _fields_ = [("point", C.c_float * 12), ("normal", C.c_float * 9), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class MotionDesc(C.Structure):
+    """rt_motion_desc: what rt_accumulate_motion takes beside rt_accumulate's (and rt_accumulate_moments') description."""
+    _fields_ = [("motion_device", C.c_void_p), ("instance_count", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+RT_MOTION_STATIC, RT_MOTION_MOVED, RT_MOTION_NO_HISTORY = 0, 1, 2
+
+
 class DenoiseGuidedDesc(C.Structure):
     """rt_denoise_guided_desc: image size, passes, sigmas, device buffers, scratch and stream of one rt_denoise_guided
     call."""
@@ -250,6 +264,7 @@ EXPORTED_SYMBOLS = (
     "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device", "rt_query_camera",
     "rt_denoise", "rt_denoise_scratch_bytes", "rt_accumulate", "rt_camera_reprojection",
     "rt_accumulate_moments", "rt_denoise_guided", "rt_denoise_guided_scratch_bytes",
+    "rt_instance_motion_records", "rt_accumulate_motion",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -289,6 +304,10 @@ def _declare(lib):
     lib.rt_accumulate.restype = C.c_int
     lib.rt_accumulate_moments.argtypes = [C.c_int, P(AccumulateDesc), P(MomentsDesc)]
     lib.rt_accumulate_moments.restype = C.c_int
+    lib.rt_accumulate_motion.argtypes = [C.c_int, P(AccumulateDesc), P(MomentsDesc), P(MotionDesc)]
+    lib.rt_accumulate_motion.restype = C.c_int
+    lib.rt_instance_motion_records.argtypes = [P(Xform), P(Xform), C.c_size_t, P(InstanceMotion)]
+    lib.rt_instance_motion_records.restype = C.c_int
     lib.rt_denoise_guided.argtypes = [C.c_int, P(DenoiseGuidedDesc)]
     lib.rt_denoise_guided.restype = C.c_int
     lib.rt_denoise_guided_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]

@@ -53,6 +53,40 @@ def reprojection(camera_input: abi.CameraInput, width: int, height: int) -> abi.
     return out
 
 
+MOTION_DTYPE = np.dtype([("point", np.float32, (3, 4)), ("normal", np.float32, (3, 3)), ("flags", np.uint32),
+                         ("reserved", np.uint32, 2)])                # rt_instance_motion, 96 bytes
+XFORM_DTYPE = np.dtype([("shift", np.float32, 3), ("rotate_deg", np.float32, 3), ("scale", np.float32, 3)])   # rt_xform
+
+
+def _xforms(x, name):
+    """An rt_xform array as numpy: a ctypes array of abi.Xform, a structured array of XFORM_DTYPE, or floats [n, 9]
+    (shift, rotate in degrees, scale)."""
+    if isinstance(x, C.Array) and issubclass(x._type_, abi.Xform):
+        return np.frombuffer(x, dtype=XFORM_DTYPE).copy()
+    a = np.asarray(x)
+    if a.dtype == XFORM_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.dtype.fields is not None or a.ndim != 2 or a.shape[1] != 9:
+        raise ValueError(f"{name}: a ctypes array of abi.Xform, a numpy array of XFORM_DTYPE or floats [n, 9]")
+    return np.ascontiguousarray(a, np.float32).view(XFORM_DTYPE).reshape(-1)
+
+
+def instance_motion(prev_xforms, cur_xforms) -> np.ndarray:
+    """rt_instance_motion_records: one record per instance that carries a world point and normal of this frame back to
+    where the instance stood in the last one (host only, no scene, no GPU), from last frame's and this frame's
+    transforms (see _xforms for the forms taken).  Returns a numpy array of MOTION_DTYPE: what Renderer.accumulate
+    takes as motion."""
+    lib = abi.load_library()
+    prev, cur = _xforms(prev_xforms, "prev_xforms"), _xforms(cur_xforms, "cur_xforms")
+    if len(prev) != len(cur):
+        raise ValueError(f"prev_xforms holds {len(prev)} transforms, cur_xforms {len(cur)}")
+    out = np.zeros(len(cur), MOTION_DTYPE)
+    as_ptr = lambda a, t: C.cast(a.ctypes.data, C.POINTER(t))
+    abi.check(lib, lib.rt_instance_motion_records(as_ptr(prev, abi.Xform), as_ptr(cur, abi.Xform), len(cur),
+                                                  as_ptr(out, abi.InstanceMotion)))
+    return out
+
+
 def hits_to_numpy(hits) -> np.ndarray:
     """The rt_hit records of Renderer.query_rays (torch uint8 [N, 48], any device) as the structured array
     Renderer.trace_rays returns."""
@@ -472,7 +506,7 @@ class Renderer:
 
     def accumulate(self, rgb, hits, prev=None, *, prev_view=None, max_history: float = ACCUMULATE_DEFAULTS[0],
                    normal_cos: float = ACCUMULATE_DEFAULTS[1], plane_tolerance: float = ACCUMULATE_DEFAULTS[2],
-                   out_rgb=None, stream=None, sync: bool = True, albedo=None, moments: bool = False):
+                   out_rgb=None, stream=None, sync: bool = True, albedo=None, moments: bool = False, motion=None):
         """rt_accumulate: temporal accumulation (include/rt.h, "Temporal accumulation") on torch CUDA tensors of the
         shapes render and query_camera produce: rgb float32 [h, w, 3] (this frame, rendered into rgb32_device) and hits
         uint8 [h, w, 48] (query_camera(want_hits=True) of this frame), contiguous and on the scene's device.  prev: the
@@ -485,7 +519,11 @@ class Renderer:
         current stream); the outputs are allocated on it, and with sync=False the call returns after the enqueue.
         moments=True is rt_accumulate_moments (include/rt.h, "Variance-guided denoising"): the same history and rgb, and
         the dict also holds "moments", float32 [h, w, 2], the first two moments of the luminance of rgb / albedo (albedo:
-        float32 [h, w, 3], optional, the one denoise_guided will be given); prev must then be a dict of such a call."""
+        float32 [h, w, 3], optional, the one denoise_guided will be given); prev must then be a dict of such a call.
+        motion: rt_accumulate_motion (include/rt.h, "Moving instances"), with or without the moments: the records of
+        rtamd.instance_motion as the numpy array it returns (uploaded on the call's stream) or as a contiguous uint8 or
+        float32 CUDA tensor of [n, 96] bytes, indexed by the hits' instance; with prev given it needs prev_view (a still
+        camera passes rtamd.reprojection of its own camera)."""
         torch, dev, stream, ctx, raw = self._torch_call(stream)
 
         rgb = checked(rgb, 3, torch.float32, "rgb", dev)
@@ -512,6 +550,21 @@ class Renderer:
             raise ValueError("prev_view: an abi.Reprojection (rtamd.reprojection)")
         if not isinstance(stream, torch.cuda.Stream):
             sync = True      # a raw hipStream_t gives torch nothing to order the outputs' allocation with (as denoise)
+        nrec = C.sizeof(abi.InstanceMotion)
+        if motion is not None:
+            if prev is not None and prev_view is None:
+                raise ValueError("motion: prev_view is needed (a still camera passes rtamd.reprojection of its own camera)")
+            if isinstance(motion, np.ndarray):
+                if motion.dtype != MOTION_DTYPE:
+                    raise ValueError("motion: a numpy array of MOTION_DTYPE (rtamd.instance_motion)")
+                host = torch.from_numpy(np.ascontiguousarray(motion).reshape(-1).view(np.uint8).reshape(-1, nrec))
+                with ctx:                         # uploaded on the call's stream
+                    motion = host.to(dev, non_blocking=False)
+            elif not (isinstance(motion, torch.Tensor) and motion.device == dev and motion.is_contiguous() and motion.dim() == 2
+                      and motion.dtype in (torch.uint8, torch.float32)
+                      and motion.shape[1] * motion.element_size() == nrec):
+                raise ValueError(f"motion: rtamd.instance_motion's array, or a contiguous uint8 / float32 tensor of [n, {nrec}] "
+                                 f"bytes on {dev}")
         d = abi.AccumulateDesc()
         d.width, d.height = w, h
         d.flags = 0 if sync else abi.RT_ACCUMULATE_NO_SYNC
@@ -533,14 +586,22 @@ class Renderer:
         if prev is not None:
             d.prev_hits_device, d.prev_history_device = prev["hits"].data_ptr(), prev["history"].data_ptr()
         d.history_device, d.rgb32_device = history.data_ptr(), out_rgb.data_ptr()
-        if not moments:
+        m = None
+        if moments:
+            m = abi.MomentsDesc()
+            m.albedo_device = albedo.data_ptr() if albedo is not None else None
+            m.prev_moments_device = prev["moments"].data_ptr() if prev is not None else None
+            m.moments_device = mom.data_ptr()
+        if motion is not None:
+            mo = abi.MotionDesc()
+            mo.instance_count = int(motion.shape[0])
+            mo.motion_device = motion.data_ptr() if mo.instance_count else None
+            abi.check(self.lib, self.lib.rt_accumulate_motion(self.device, C.byref(d), C.byref(m) if moments else None,
+                                                              C.byref(mo)))
+        elif moments:
+            abi.check(self.lib, self.lib.rt_accumulate_moments(self.device, C.byref(d), C.byref(m)))
+        else:
             abi.check(self.lib, self.lib.rt_accumulate(self.device, C.byref(d)))
-            return res
-        m = abi.MomentsDesc()
-        m.albedo_device = albedo.data_ptr() if albedo is not None else None
-        m.prev_moments_device = prev["moments"].data_ptr() if prev is not None else None
-        m.moments_device = mom.data_ptr()
-        abi.check(self.lib, self.lib.rt_accumulate_moments(self.device, C.byref(d), C.byref(m)))
         return res
 
     def denoise_guided(self, acc, albedo=None, *, iterations: int = 5, sigma_luminance: float = GUIDED_SIGMAS[0],
