@@ -40,7 +40,8 @@ extern "C" {
  *     rt_accumulate_moments / rt_moments_desc / rt_denoise_guided / rt_denoise_guided_scratch_bytes /
  *     rt_denoise_guided_desc arrived within 5 the same way;
  *     rt_instance_motion_records / rt_instance_motion / rt_accumulate_motion / rt_motion_desc arrived within 5 the same
- *     way) */
+ *     way;
+ *     rt_denoise_guided_feedback / rt_feedback_desc arrived within 5 the same way) */
 #define RT_ABI_VERSION 5u
 
 typedef enum rt_status {
@@ -552,11 +553,14 @@ rt_status rt_denoise(int device, const rt_denoise_desc *desc);
  *            compensate instance motion (a moved instance is caught by the plane test, so its pixels restart):
  *            rt_accumulate_motion below does.  Shadows and reflections of a moving instance on static pixels are not
  *            compensated by either: the surface has not moved, so its history is kept while its shading changes.
- *            (Luminance moments and the variance-guided filter: rt_accumulate_moments and rt_denoise_guided below.)
+ *            (Luminance moments and the variance-guided filter: rt_accumulate_moments and rt_denoise_guided below;
+ *            the filtered colour as next frame's history: rt_denoise_guided_feedback, "History feedback" below.)
  * Outputs  : history_device (required): float4 per pixel, next frame's prev_history_device.  rgb32_device (optional):
  *            3 floats per pixel, out.rgb; it may be color_device itself (a thread reads only its own pixel's colour).
  *            Otherwise no output may overlap an input or the other output: the byte ranges are compared on the host.
- *            So the caller ping-pongs two history buffers and two hits buffers.
+ *            So the caller ping-pongs two history buffers and two hits buffers.  (The one other exact alias the
+ *            filters allow: rt_denoise_guided_feedback's feedback_device may be its history_device, "History feedback"
+ *            below, for the same reason.)
  * Ordering : as rt_denoise, with RT_ACCUMULATE_NO_SYNC for RT_DENOISE_NO_SYNC.
  * Errors   : all before anything is enqueued, the argument checks first (they answer without a GPU):
  *            RT_ERR_INVALID_ARGUMENT for a NULL desc, reserved or reserved1 != 0, unknown flags, width or height above
@@ -656,11 +660,11 @@ rt_status rt_accumulate(int device, const rt_accumulate_desc *desc);
  *            the box |dx|, |dy| <= 2 (2^iterations - 1) around it, across the hit / sky boundary too (0 * NaN), and
  *            to no other pixel; v_0 reads no colour and is unaffected.  Non-finite moments are not detected either
  *            and their effect is unspecified (an infinite variance gives k(p) = 0 and a finite result).
- * Not done : the filtered colour of the first pass is not fed back as history (SVGF does); moving instances are
- *            compensated by rt_accumulate_motion ("Moving instances" below), not by rt_accumulate_moments, and the
- *            shadows and reflections a moving instance casts on static pixels by neither; the colour accumulates
- *            modulated while the moments are demodulated, so where the albedo changes under a kept pixel the two
- *            disagree for up to max_history frames. */
+ * Not done : moving instances are compensated by rt_accumulate_motion ("Moving instances" below), not by
+ *            rt_accumulate_moments, and the shadows and reflections a moving instance casts on static pixels by
+ *            neither; the colour accumulates modulated while the moments are demodulated, so where the albedo changes
+ *            under a kept pixel the two disagree for up to max_history frames.  (The filtered colour as history:
+ *            rt_denoise_guided_feedback, "History feedback" below.) */
 typedef struct rt_moments_desc {
     const float *albedo_device;        /* optional, 3 floats per pixel: the albedo the guided filter will be given */
     const float *prev_moments_device;  /* last call's moments_device; NULL exactly when desc->prev_history_device is NULL */
@@ -691,6 +695,41 @@ typedef struct rt_denoise_guided_desc {
 
 uint64_t  rt_denoise_guided_scratch_bytes(uint32_t width, uint32_t height);
 rt_status rt_denoise_guided(int device, const rt_denoise_guided_desc *desc);
+
+/* History feedback, as SVGF has it: the colour the guided filter's first pass leaves becomes the next frame's temporal
+ * history in place of the accumulated one-sample colour, so what is accumulated from then on has been filtered once
+ * per frame it went through.  The pass is fixed at the first one: on the float32 restatement (tests/feedback_ref.py)
+ * a later pass removes no more flicker and costs far more error.
+ *
+ * rt_denoise_guided_feedback does all of rt_denoise_guided(device, desc): the same argument checks, ordering,
+ * RT_DENOISE_NO_SYNC and scratch; rgb32_device, rgba8_device and variance_device receive the same bits.  Its first
+ * pass (one kernel, instantiated with and without the feedback) also writes, for every pixel k, sky included:
+ *              feedback[k] = (c_1(p) a(p), history[k].w)
+ *            c_1 a: per channel the product the same call with iterations = 1 writes to rgb32_device (c_1 without
+ *            albedo); with iterations = 1 the outputs and the feedback are the same three products.  .w: the history
+ *            texel's length, copied as bits.
+ *            The caller passes feedback_device as the next frame's prev_history_device; rt_accumulate*, the moments and
+ *            rt_denoise_guided_desc do not change.  tests/feedback_ref.py restates the chain.
+ * Variance : the moments still accumulate the unfiltered samples, so v_0 = v_t / N describes the unfiltered mean of N
+ *            samples and overstates the variance of a fed-back history.  The filter therefore errs towards more blur:
+ *            where the signal varies faster than the filter's reach the error rises frame by frame while the flicker
+ *            falls (profiles/feedback/README.md has both cases).  A trade-off that depends on the scene, not a default.
+ * Outputs  : feedback_device (required): float4 per pixel, 16-byte aligned.  It may be exactly desc->history_device:
+ *            the pack kernel has copied the history's colour into the scratch before the first pass writes, all on one
+ *            stream, and a texel's length is read by the thread that then writes that texel (the rule that lets
+ *            rt_accumulate's rgb32_device be color_device).  Any other overlap with an input, another output or the
+ *            scratch, a partial overlap with the history included, is an error.
+ * Errors   : rt_denoise_guided's, and, before anything is enqueued and without a GPU, RT_ERR_INVALID_ARGUMENT for a
+ *            NULL feedback, reserved != 0, a NULL feedback_device, a feedback_device that is not 16-byte aligned, the
+ *            overlaps above; then for a feedback_device the device cannot access.  width * height == 0 returns RT_OK
+ *            and touches no device. */
+typedef struct rt_feedback_desc {
+    float   *feedback_device;  /* required output: float4 {r, g, b, length} per pixel, 16-byte aligned */
+    uint64_t reserved;         /* 0 */
+} rt_feedback_desc;            /* 16 bytes */
+
+rt_status rt_denoise_guided_feedback(int device, const rt_denoise_guided_desc *desc,
+                                     const rt_feedback_desc *feedback);
 
 /* Moving instances: rt_accumulate and rt_accumulate_moments reproject a pixel's hit point as if the surface had stood
  * still, so on an instance that moved the point lands on a previous record of where the surface was, the plane test

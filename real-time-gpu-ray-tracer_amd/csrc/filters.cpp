@@ -1,8 +1,8 @@
 // filters.cpp — the image filters: rt_denoise (denoise.hip), rt_accumulate / _moments / _motion (accumulate.hip) and
-// rt_denoise_guided (guided.hip).  They take no scene: `int device` and a descriptor of caller buffers.  Every call has
-// the same shape: the argument checks, which need no device and come in the order the ABI tests pin; the device and the
-// buffers' accessibility from it; the launcher; the tail.  rt_instance_motion_records, the host-only helper that feeds
-// rt_accumulate_motion, is here too (its arithmetic: instance_motion.hpp).
+// rt_denoise_guided / _feedback (guided.hip).  They take no scene: `int device` and a descriptor of caller buffers.
+// Every call has the same shape: the argument checks, which need no device and come in the order the ABI tests pin; the
+// device and the buffers' accessibility from it; the launcher; the tail.  rt_instance_motion_records, the host-only
+// helper that feeds rt_accumulate_motion, is here too (its arithmetic: instance_motion.hpp).
 #include "instance_motion.hpp"
 #include "launch.hpp"
 #include "scene.hpp"
@@ -124,6 +124,65 @@ rt_status accumulate_call(int device, const rt_accumulate_desc *d, const rt_mome
     return finish(st, (d->flags & RT_ACCUMULATE_NO_SYNC) != 0);
 }
 
+// rt_denoise_guided (f == nullptr, with_feedback false) and rt_denoise_guided_feedback: one set of checks, one launcher
+rt_status guided_call(int device, const rt_denoise_guided_desc *d, const rt_feedback_desc *f, bool with_feedback) {
+    const std::string name = with_feedback ? "rt_denoise_guided_feedback" : "rt_denoise_guided";
+    // the argument checks need no device
+    if (!d || (with_feedback && !f)) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (d->reserved != 0 || (d->flags & ~(uint32_t)RT_DENOISE_NO_SYNC) || (f && f->reserved != 0))
+        return fail(RT_ERR_INVALID_ARGUMENT, name + ": reserved bits set");
+    if (d->iterations < 1 || d->iterations > 5) return fail(RT_ERR_INVALID_ARGUMENT, name + ": iterations must be in 1..5");
+    if (!(d->sigma_luminance > 0.0f) || !(d->sigma_normal > 0.0f) || !(d->sigma_plane > 0.0f))
+        return fail(RT_ERR_INVALID_ARGUMENT, name + ": every sigma must be > 0 (+inf switches its term off)");
+    if (d->width > 16384 || d->height > 16384) return fail(RT_ERR_INVALID_ARGUMENT, name + ": width and height are at most 16384");
+    if (!d->rgb32_device && !d->rgba8_device) return fail(RT_ERR_INVALID_ARGUMENT, name + ": no output buffer");
+    if (!d->history_device || !d->moments_device || !d->hits_device || !d->scratch_device || (f && !f->feedback_device))
+        return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+    if (d->scratch_bytes < scratch_bytes(d->width, d->height))
+        return fail(RT_ERR_INVALID_ARGUMENT, name + ": scratch_bytes is less than rt_denoise_guided_scratch_bytes(width, height)");
+    if (((uintptr_t)d->scratch_device | (uintptr_t)d->history_device) & 15u)
+        return fail(RT_ERR_INVALID_ARGUMENT, name + ": the scratch and the history must be 16-byte aligned");
+    if (f && ((uintptr_t)f->feedback_device & 15u))
+        return fail(RT_ERR_INVALID_ARGUMENT, name + ": feedback_device must be 16-byte aligned");
+    if ((uintptr_t)d->moments_device & 7u) return fail(RT_ERR_INVALID_ARGUMENT, name + ": the moments must be 8-byte aligned");
+    if (((uintptr_t)d->hits_device | (uintptr_t)d->albedo_device | (uintptr_t)d->rgb32_device | (uintptr_t)d->rgba8_device |
+         (uintptr_t)d->variance_device) & 3u)
+        return fail(RT_ERR_INVALID_ARGUMENT, name + ": the buffers must be 4-byte aligned");
+    // no output (the scratch is one) may overlap an input or another output; the feedback may be the history itself
+    const uint64_t n = (uint64_t)d->width * d->height;
+    float *const feedback = f ? f->feedback_device : nullptr;
+    const Range history{d->history_device, 16 * n};
+    const Range in[] = {{d->moments_device, 8 * n}, {d->hits_device, sizeof(rt_hit) * n}, {d->albedo_device, 12 * n}};
+    const Range out[] = {{d->rgb32_device, 12 * n}, {d->rgba8_device, 4 * n}, {d->variance_device, 4 * n},
+                         {d->scratch_device, DENOISE_SCRATCH_PER_PIXEL * n}, {feedback, 16 * n}};
+    bool clash = false;
+    for (size_t i = 0; i < 5; i++) {
+        const bool in_place = i == 4 && out[i].p == history.p;
+        clash = clash || (!in_place && overlap(out[i], history));
+        for (const Range &r : in) clash = clash || overlap(out[i], r);
+        for (size_t j = i + 1; j < 5; j++) clash = clash || overlap(out[i], out[j]);
+    }
+    if (clash) return fail(RT_ERR_INVALID_ARGUMENT, name + ": an output overlaps another buffer");
+    if (n == 0) return RT_OK;
+    DeviceRestore restore;
+    RT_TRY(select_device(device));
+    RT_TRY(all_accessible({d->history_device, d->moments_device, d->hits_device, d->albedo_device, d->rgb32_device,
+                           d->rgba8_device, d->variance_device, d->scratch_device, feedback},
+                          device, name + ": a buffer is not accessible from the device"));
+
+    GuidedGPU g{};
+    g.history = reinterpret_cast<const float4 *>(d->history_device);
+    g.moments = reinterpret_cast<const float2 *>(d->moments_device);
+    g.hits = d->hits_device; g.albedo = d->albedo_device;
+    g.rgb = d->rgb32_device; g.rgba = static_cast<uint32_t *>(d->rgba8_device); g.variance = d->variance_device;
+    split_scratch(g, d->scratch_device, n);
+    g.w = d->width; g.h = d->height;
+    hipStream_t st = static_cast<hipStream_t>(d->stream);
+    HIP_TRY(launch_denoise_guided(g, d->iterations, d->sigma_luminance, d->sigma_normal, d->sigma_plane,
+                                  reinterpret_cast<float4 *>(feedback), st));
+    return finish(st, (d->flags & RT_DENOISE_NO_SYNC) != 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -182,57 +241,10 @@ rt_status rt_instance_motion_records(const rt_xform *prev, const rt_xform *cur, 
 
 uint64_t rt_denoise_guided_scratch_bytes(uint32_t width, uint32_t height) { return scratch_bytes(width, height); }
 
-rt_status rt_denoise_guided(int device, const rt_denoise_guided_desc *d) {
-    // the argument checks need no device
-    if (!d) return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (d->reserved != 0 || (d->flags & ~(uint32_t)RT_DENOISE_NO_SYNC))
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: reserved bits set");
-    if (d->iterations < 1 || d->iterations > 5) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: iterations must be in 1..5");
-    if (!(d->sigma_luminance > 0.0f) || !(d->sigma_normal > 0.0f) || !(d->sigma_plane > 0.0f))
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: every sigma must be > 0 (+inf switches its term off)");
-    if (d->width > 16384 || d->height > 16384)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: width and height are at most 16384");
-    if (!d->rgb32_device && !d->rgba8_device) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: no output buffer");
-    if (!d->history_device || !d->moments_device || !d->hits_device || !d->scratch_device)
-        return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-    if (d->scratch_bytes < scratch_bytes(d->width, d->height))
-        return fail(RT_ERR_INVALID_ARGUMENT,
-                    "rt_denoise_guided: scratch_bytes is less than rt_denoise_guided_scratch_bytes(width, height)");
-    if (((uintptr_t)d->scratch_device | (uintptr_t)d->history_device) & 15u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: the scratch and the history must be 16-byte aligned");
-    if ((uintptr_t)d->moments_device & 7u) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: the moments must be 8-byte aligned");
-    if (((uintptr_t)d->hits_device | (uintptr_t)d->albedo_device | (uintptr_t)d->rgb32_device | (uintptr_t)d->rgba8_device |
-         (uintptr_t)d->variance_device) & 3u)
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: the buffers must be 4-byte aligned");
-    // no output (the scratch is one) may overlap an input or another output
-    const uint64_t n = (uint64_t)d->width * d->height;
-    const Range in[] = {{d->history_device, 16 * n}, {d->moments_device, 8 * n}, {d->hits_device, sizeof(rt_hit) * n},
-                        {d->albedo_device, 12 * n}};
-    const Range out[] = {{d->rgb32_device, 12 * n}, {d->rgba8_device, 4 * n}, {d->variance_device, 4 * n},
-                         {d->scratch_device, DENOISE_SCRATCH_PER_PIXEL * n}};
-    bool clash = false;
-    for (size_t i = 0; i < 4; i++) {
-        for (const Range &r : in) clash = clash || overlap(out[i], r);
-        for (size_t j = i + 1; j < 4; j++) clash = clash || overlap(out[i], out[j]);
-    }
-    if (clash) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_guided: an output overlaps another buffer");
-    if (n == 0) return RT_OK;
-    DeviceRestore restore;
-    RT_TRY(select_device(device));
-    RT_TRY(all_accessible({d->history_device, d->moments_device, d->hits_device, d->albedo_device, d->rgb32_device,
-                           d->rgba8_device, d->variance_device, d->scratch_device},
-                          device, "rt_denoise_guided: a buffer is not accessible from the device"));
+rt_status rt_denoise_guided(int device, const rt_denoise_guided_desc *d) { return guided_call(device, d, nullptr, false); }
 
-    GuidedGPU g{};
-    g.history = reinterpret_cast<const float4 *>(d->history_device);
-    g.moments = reinterpret_cast<const float2 *>(d->moments_device);
-    g.hits = d->hits_device; g.albedo = d->albedo_device;
-    g.rgb = d->rgb32_device; g.rgba = static_cast<uint32_t *>(d->rgba8_device); g.variance = d->variance_device;
-    split_scratch(g, d->scratch_device, n);
-    g.w = d->width; g.h = d->height;
-    hipStream_t st = static_cast<hipStream_t>(d->stream);
-    HIP_TRY(launch_denoise_guided(g, d->iterations, d->sigma_luminance, d->sigma_normal, d->sigma_plane, st));
-    return finish(st, (d->flags & RT_DENOISE_NO_SYNC) != 0);
+rt_status rt_denoise_guided_feedback(int device, const rt_denoise_guided_desc *d, const rt_feedback_desc *f) {
+    return guided_call(device, d, f, true);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// guided.hip — rt_denoise_guided: the a-trous filter of denoise.hip steered by a per-pixel variance of the accumulated
-// colour, in the manner of SVGF (Schied et al. 2017).  include/rt.h ("Variance-guided denoising") states the filter;
+// guided.hip — rt_denoise_guided and rt_denoise_guided_feedback: the a-trous filter of denoise.hip steered by a
+// per-pixel variance of the accumulated colour, in the manner of SVGF (Schied et al. 2017).  include/rt.h
+// ("Variance-guided denoising") states the filter;
 // tests/guided_ref.py restates it in numpy with this file's operation order.  Built with -ffp-contract=off: every
 // product and sum rounds where the reference's does, so a result differs from the float32 restatement only through
 // expf.  The staged tile, the staged row, the scratch planes and the leaf functions it shares with denoise.hip:
@@ -24,7 +25,12 @@
 //     row form       steps 4, 8 and 16: the staged row.  Rows y - 1 and y + 1 are not among the tap rows, so the nine
 //                    variances come from the source plane by direct loads (4 bytes each, from lines the previous
 //                    pass has just written).
-// Pixel indices are size_t.  No scratch memory and no spills (profiles/guided/kernel_resources.txt).
+//   feedback         rt_denoise_guided_feedback (include/rt.h, "History feedback"): a second instantiation of the
+//                    step-1 pass also writes its result times the albedo, with the history's length, as next frame's
+//                    history: 16 B per pixel more written and, unless it is the last pass, the albedo's 12 B read.
+//                    The other kernels are the same code for both calls.
+// Pixel indices are size_t.  No scratch memory and no spills (profiles/guided/kernel_resources.txt, and
+// profiles/feedback/kernel_resources.txt for the feedback pass).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -92,6 +98,34 @@ __device__ __forceinline__ void write_result(const GuidedGPU &g, const GuidedPas
         return;
     }
     write_outputs(g.albedo, g.rgb, g.rgba, i, r, gr, b);
+}
+
+// The first pass of rt_denoise_guided_feedback: write_result, and {the result times the albedo, the history's length}
+// into `feedback`, next frame's prev_history.  With iterations = 1 the outputs and the feedback are the same three
+// products.  `feedback` may be g.history itself: the pack kernel has read the colour, and the length is read here by
+// the one thread that then writes the texel.  (The albedo's floor and the stores: as atrous.hpp's write_outputs.)
+__device__ __forceinline__ void write_result_feedback(const GuidedGPU &g, const GuidedPass &ps, float4 *__restrict__ dst,
+                                                      float4 *feedback, size_t i, const GuidedSums &s) {
+    const float r = s.r / s.w, gr = s.g / s.w, b = s.b / s.w;
+    float ar = 1.0f, ag = 1.0f, ab = 1.0f;
+    if (g.albedo) {
+        ar = fmaxf(g.albedo[3 * i + 0], AT_ALBEDO_FLOOR);
+        ag = fmaxf(g.albedo[3 * i + 1], AT_ALBEDO_FLOOR);
+        ab = fmaxf(g.albedo[3 * i + 2], AT_ALBEDO_FLOOR);
+    }
+    const float o0 = r * ar, o1 = gr * ag, o2 = b * ab;
+    const float length = reinterpret_cast<const float *>(g.history + i)[3];
+    feedback[i] = make_float4(o0, o1, o2, length);
+    if (!ps.last) {
+        dst[i] = make_float4(r, gr, b, s.v / (s.w * s.w));
+        return;
+    }
+    if (g.rgb) {
+        g.rgb[3 * i + 0] = o0;
+        g.rgb[3 * i + 1] = o1;
+        g.rgb[3 * i + 2] = o2;
+    }
+    if (g.rgba) g.rgba[i] = quantise(o0, o1, o2);
 }
 
 __global__ __launch_bounds__(256) void guided_pack_kernel(GuidedGPU g) {
@@ -213,9 +247,9 @@ __global__ __launch_bounds__(256) void guided_variance_direct_kernel(GuidedGPU g
     if (g.variance) g.variance[p] = v;
 }
 
-template <int STEP>
+template <int STEP, bool FEEDBACK>
 __device__ __forceinline__ void filter_lds(const GuidedGPU &g, const GuidedPass &ps, const float4 *__restrict__ src,
-                                           float4 *__restrict__ dst) {
+                                           float4 *__restrict__ dst, float4 *feedback = nullptr) {
     constexpr int HALO = 2 * STEP, EDGE = AT_TILE + 2 * HALO;
     static_assert(EDGE <= AT_PITCH, "the staged row does not fit its pitch");
     __shared__ float4 sc[EDGE * AT_PITCH], sn[EDGE * AT_PITCH], sx[EDGE * AT_PITCH];
@@ -269,16 +303,25 @@ __device__ __forceinline__ void filter_lds(const GuidedGPU &g, const GuidedPass 
             }
         }
     }
-    write_result(g, ps, dst, (size_t)y * g.w + (size_t)x, s);
+    if (FEEDBACK)
+        write_result_feedback(g, ps, dst, feedback, (size_t)y * g.w + (size_t)x, s);
+    else
+        write_result(g, ps, dst, (size_t)y * g.w + (size_t)x, s);
 }
 
 __global__ __launch_bounds__(256) void guided_filter_lds1_kernel(GuidedGPU g, GuidedPass ps, const float4 *__restrict__ src,
                                                                  float4 *__restrict__ dst) {
-    filter_lds<1>(g, ps, src, dst);
+    filter_lds<1, false>(g, ps, src, dst);
+}
+// rt_denoise_guided_feedback's first pass
+__global__ __launch_bounds__(256) void guided_filter_lds1_feedback_kernel(GuidedGPU g, GuidedPass ps,
+                                                                          const float4 *__restrict__ src,
+                                                                          float4 *__restrict__ dst, float4 *feedback) {
+    filter_lds<1, true>(g, ps, src, dst, feedback);
 }
 __global__ __launch_bounds__(256) void guided_filter_lds2_kernel(GuidedGPU g, GuidedPass ps, const float4 *__restrict__ src,
                                                                  float4 *__restrict__ dst) {
-    filter_lds<2>(g, ps, src, dst);
+    filter_lds<2, false>(g, ps, src, dst);
 }
 
 // The row form (atrous.hpp, "the staged row")
@@ -342,7 +385,7 @@ char prep_form() {
 }  // namespace
 
 hipError_t launch_denoise_guided(const GuidedGPU &g, uint32_t iterations, float sigma_luminance, float sigma_normal,
-                                 float sigma_plane, hipStream_t stream) {
+                                 float sigma_plane, float4 *feedback, hipStream_t stream) {
     const size_t n = (size_t)g.w * g.h;
     GuidedPass ps{};
     ps.sigma_l = sigma_luminance;
@@ -364,7 +407,9 @@ hipError_t launch_denoise_guided(const GuidedGPU &g, uint32_t iterations, float 
         ps.last = i + 1 == iterations ? 1u : 0u;
         const float4 *src = g.plane[i & 1u];
         float4 *dst = g.plane[(i + 1u) & 1u];
-        if (ps.step == 1)
+        if (ps.step == 1 && feedback)
+            hipLaunchKernelGGL(guided_filter_lds1_feedback_kernel, tiles, dim3(256), 0, stream, g, ps, src, dst, feedback);
+        else if (ps.step == 1)
             hipLaunchKernelGGL(guided_filter_lds1_kernel, tiles, dim3(256), 0, stream, g, ps, src, dst);
         else if (ps.step == 2)
             hipLaunchKernelGGL(guided_filter_lds2_kernel, tiles, dim3(256), 0, stream, g, ps, src, dst);

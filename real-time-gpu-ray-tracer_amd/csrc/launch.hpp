@@ -111,9 +111,13 @@ struct GuidedGPU {
     float4 *g0, *g1;
     uint32_t w, h;
 };
-// the pack and variance passes and `iterations` (1..5) filter passes, the last one writing the outputs
+// the pack and variance passes and `iterations` (1..5) filter passes, the last one writing the outputs.  feedback
+// (rt_denoise_guided_feedback; nullptr: none): the first pass also writes {its result times the albedo, the history's
+// length} there, and it may be g.history itself.  It is an argument of that pass's kernel alone and not a member of
+// GuidedGPU: the filter kernels take their pass after the struct, so a member would move every later argument and
+// with it the code of the kernels that were there (profiles/feedback/README.md)
 hipError_t launch_denoise_guided(const GuidedGPU &g, uint32_t iterations, float sigma_luminance, float sigma_normal,
-                                 float sigma_plane, hipStream_t stream);
+                                 float sigma_plane, float4 *feedback, hipStream_t stream);
 
 // One flavour's launchers.  RT_RENDER_EXACT / RT_QUERY_EXACT win over option "fast_math".
 struct TraceFlavour {

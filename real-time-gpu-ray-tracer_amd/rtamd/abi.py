@@ -203,6 +203,11 @@ class DenoiseGuidedDesc(C.Structure):
                 ("scratch_bytes", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class FeedbackDesc(C.Structure):
+    """rt_feedback_desc: what rt_denoise_guided_feedback takes beside rt_denoise_guided's description."""
+    _fields_ = [("feedback_device", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 class TriangleUpdate(C.Structure):
     """rt_triangle_update: triangle range, device vertex / normal streams and stream of one
     rt_scene_update_triangles_device call."""
@@ -264,7 +269,7 @@ EXPORTED_SYMBOLS = (
     "rt_box_test", "rt_query_rays", "rt_scene_update_triangles_device", "rt_query_camera",
     "rt_denoise", "rt_denoise_scratch_bytes", "rt_accumulate", "rt_camera_reprojection",
     "rt_accumulate_moments", "rt_denoise_guided", "rt_denoise_guided_scratch_bytes",
-    "rt_instance_motion_records", "rt_accumulate_motion",
+    "rt_instance_motion_records", "rt_accumulate_motion", "rt_denoise_guided_feedback",
 )
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -310,6 +315,8 @@ def _declare(lib):
     lib.rt_instance_motion_records.restype = C.c_int
     lib.rt_denoise_guided.argtypes = [C.c_int, P(DenoiseGuidedDesc)]
     lib.rt_denoise_guided.restype = C.c_int
+    lib.rt_denoise_guided_feedback.argtypes = [C.c_int, P(DenoiseGuidedDesc), P(FeedbackDesc)]
+    lib.rt_denoise_guided_feedback.restype = C.c_int
     lib.rt_denoise_guided_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
     lib.rt_denoise_guided_scratch_bytes.restype = C.c_uint64
     lib.rt_camera_reprojection.argtypes = [P(CameraInput), C.c_uint32, C.c_uint32, P(Reprojection)]
